@@ -28,9 +28,14 @@ step needs); a failed check sends every rank to RCCL, and a failed 
 window exits non-zero without a line.  A barrier + device sync bracket the timed region and the
 time is the MAX over ranks.
 
-Also reported: the dominant kernel's roofline (algorithmic FP64 flops / its average launch
-time measured with HIP events on the launch stream) and the CPU oracle timed on this host
-(cpu_baseline, rank 0 only).
+A plain run sets up, warms up, times the steps and prints the result line (headline figure, the
+window's configuration and reset accounting).  ``--dump-outputs DIR`` also writes what the last
+timed step returned (rank 0's envs) as DIR/<name>.npy.
+
+``--full`` adds, after the window: the dominant kernel's roofline (algorithmic FP64 flops / its
+average launch time measured with HIP events on the launch stream), the parity probe against the
+CPU oracle and the CPU oracle timed on this host (cpu_baseline, rank 0 only; --no-cpu-baseline
+leaves the two CPU legs out).
 """
 import argparse
 import gc
@@ -82,7 +87,14 @@ def parse():
                          "5 = 65 536 envs, compliant, fixed-step RK4 at h = 2.5 mm (4x finer)")
     ap.add_argument("--envs", type=int, default=None, help="environments per GPU (default: the config's)")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the window also measure the dominant kernel's roofline (runs of its own), the "
+                         "parity probe against the CPU oracle and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0's envs) as DIR/<name>.npy, float32 / "
+                         "float64, at most 64 MB in all (a fixed, seeded sample of the envs beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave out the parity probe and the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--profile-only", action="store_true", help="no timing extras (for rocprofv3)")
     ap.add_argument("--refill-interval", type=int, default=None,
@@ -219,6 +231,46 @@ def make_actions(env, k, seed):
     hi = torch.tensor(env.action_space.high, device=env.device)
     return [((torch.rand((env.num_envs, 6), generator=g, device=env.device) * 2 - 1) * hi).contiguous()
             for _ in range(k)]
+
+
+DUMP_MAX_BYTES = 60 * 1000 * 1000     # of array data: the files stay under 64 MB with their headers
+
+
+def dump_outputs(env, path, seed):
+    """What CtrReachVecEnv.step returned for the last step run (the env's persistent output
+    buffers: step_raw and the captured graph write the same ones), one <name>.npy per array,
+    float64 where the env computes in float64 and float32 otherwise.  The terminal_* rows of envs
+    that did not finish in that step are zeroed (step() defines them for done envs only).  Above
+    DUMP_MAX_BYTES in all, the same seeded sample of the envs (ascending ids, env_ids.npy) is
+    written for every array."""
+    import numpy as np
+    import torch
+    done = env.done.bool()
+    arrays = {
+        "observation": env.obs, "achieved_goal": env.achieved_goal, "desired_goal": env.desired_goal,
+        "reward": env.reward, "done": env.done, "is_success": env.success, "error": env.error,
+        "terminal_observation": torch.where(done[:, None], env.terminal_obs, torch.zeros_like(env.terminal_obs)),
+        "terminal_achieved_goal": torch.where(done[:, None], env.terminal_achieved,
+                                              torch.zeros_like(env.terminal_achieved)),
+        "status": env.status, "joints": env.joints,
+    }
+    if env.packed_bufs is not None:
+        arrays["packed_outputs"] = env.packed_outputs()
+    n = env.num_envs
+    host = {}
+    for k, v in arrays.items():
+        v = v.detach()
+        host[k] = v.to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy()
+    row_bytes = sum(a.nbytes // n for a in host.values()) + 8
+    rows = DUMP_MAX_BYTES // row_bytes
+    ids = np.arange(n, dtype=np.int64)
+    if rows < n:
+        ids = np.sort(np.random.default_rng(seed).choice(n, size=rows, replace=False)).astype(np.int64)
+        host = {k: a[ids] for k, a in host.items()}
+    host["env_ids"] = (ids + env.env_base).astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
 
 
 CONFIGS = {
@@ -519,7 +571,12 @@ def main():
     pre = max(pre, -(-(done_pre + R) // R) * R)
     for i in range(done_pre, pre):
         one_step(i)
-    use_graph = args.graph == "on" or (args.graph == "auto" and not gather)
+    # a captured period replays whole: an even number of steps (capture_steps) that divides --steps,
+    # so that the window holds exactly --steps steps; auto launches step by step otherwise
+    graph_fits = R % 2 == 0 and args.steps % R == 0
+    if args.graph == "on" and not graph_fits:
+        raise SystemExit("--graph on needs an even refill interval (%d) that divides --steps (%d)" % (R, args.steps))
+    use_graph = args.graph == "on" or (args.graph == "auto" and not gather and graph_fits)
     graph = None
     if use_graph:
         # one refill period (R steps, the pool refill at its end) captured once; the window replays
@@ -562,6 +619,8 @@ def main():
         dist.barrier()
     el_local = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, args.dump_outputs, args.seed)      # before anything steps the env again
     if backend_used in ("push", "sdma"):
         # the window's last gather, checked where it landed: this rank's slot holds every rank's
         # rows of the last timed step (consumer wait, then a bit-exact compare with the gloo/RCCL
@@ -579,7 +638,6 @@ def main():
                 dist.destroy_process_group()
             return 3
     el = D.max_over_ranks(el_local, device=dev if backend in (None, "nccl") else "cpu")
-    traffic, traffic_note = measured_traffic(n, cfgd, systems) if ws == 1 else (None, None)
     resets_local = int((env.epoch.to(torch.int64).sum() - epoch0).item())
     refills = env.refills - refills0
     sweeps = env.sweeps - sweeps0
@@ -594,8 +652,9 @@ def main():
     # after a refill): R - 1 back-to-back step launches bracketed by one event pair on the launch
     # stream, no refill among them (the R-th step, untimed, brings the refill that falls due).
     # Without the per-step gather only (its steps also wait for / launch the gather).
+    # --full only (every rank, as the window: the ranks' GPUs stay equally loaded)
     k_ms_pooled = None
-    if not gather and R_steps > 1 and env._steps_since_refill == 0:
+    if args.full and not gather and R_steps > 1 and env._steps_since_refill == 0:
         ep0, ep1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ep0.record(stream)
         for i in range(R_steps - 1):
@@ -609,27 +668,29 @@ def main():
     # ctr_step with autoreset = 0 launches exactly one kernel (k_step) on `stream`; one event pair
     # brackets k_iters back-to-back launches (per-launch event pairs add their own few us), so the
     # average includes the ~1.5 us launch boundaries and slightly over-states the kernel time.
-    j_probe = env.joints.clone()
-    flops_env_step, sincos, nfev_mean = fk_work(env, j_probe)
-    k_iters = 32
-    sp = _abi.stream_ptr(stream)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for i in range(256):             # untimed: back to sustained-load clocks after fk_work's host sync
-        _abi.check(env.lib.ctr_step(env.cfg, env._batch, _abi.ptr(acts[i % len(acts)]), env._out, 0, sp), "ctr_step")
-    env.joints.copy_(j_probe)        # the timed launches start from the state fk_work priced
-    e0.record(stream)
-    for i in range(k_iters):
-        rc = env.lib.ctr_step(env.cfg, env._batch, _abi.ptr(acts[i % len(acts)]), env._out, 0, sp)
-        _abi.check(rc, "ctr_step")
-    e1.record(stream)
-    torch.cuda.synchronize()
-    k_ms = e0.elapsed_time(e1) / k_iters
+    # --full only.
+    if args.full:
+        j_probe = env.joints.clone()
+        flops_env_step, sincos, nfev_mean = fk_work(env, j_probe)
+        k_iters = 32
+        sp = _abi.stream_ptr(stream)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for i in range(256):             # untimed: back to sustained-load clocks after fk_work's host sync
+            _abi.check(env.lib.ctr_step(env.cfg, env._batch, _abi.ptr(acts[i % len(acts)]), env._out, 0, sp),
+                       "ctr_step")
+        env.joints.copy_(j_probe)        # the timed launches start from the state fk_work priced
+        e0.record(stream)
+        for i in range(k_iters):
+            rc = env.lib.ctr_step(env.cfg, env._batch, _abi.ptr(acts[i % len(acts)]), env._out, 0, sp)
+            _abi.check(rc, "ctr_step")
+        e1.record(stream)
+        torch.cuda.synchronize()
+        k_ms = e0.elapsed_time(e1) / k_iters
 
     if rank != 0:
         if dist:
             dist.destroy_process_group()
         return 0
-    achieved_tf = flops_env_step / (k_ms * 1e-3) / 1e12
     out = {
         "metric": "env-steps/sec at 65 536 parallel 3-tube envs; tip-pos L2 vs CPU ref",
         "value": total_steps / el,
@@ -683,61 +744,64 @@ def main():
                                     "refills_in_window_per_rank": refills,
                                     "miss_sweep_launches_in_window_per_rank": sweeps,
                                     "mean_episode_steps_est": (total_steps / resets) if resets else None}},
-        "roofline": {"bound": "valu", "achieved": achieved_tf, "peak": PEAK_FP64_VALU, "unit": "TFLOP/s",
-                     "frac": achieved_tf / PEAK_FP64_VALU, "traffic": traffic,
-                     "traffic_source": traffic_note,
-                     "kernel": "k_step", "kernel_ms": k_ms,
-                     "kernel_autoreset": "off (achieved / frac time k_step with CTR_AUTORESET_OFF: 32 back-to-back "
-                                         "launches from the window's joints, the FK work priced on those joints)",
-                     "kernel_ms_autoreset_pooled": k_ms_pooled,
-                     "frac_autoreset_pooled": (flops_env_step / (k_ms_pooled * 1e-3) / 1e12 / PEAK_FP64_VALU
-                                               if k_ms_pooled else None),
-                     "kernel_ms_autoreset_pooled_note": ("k_step as the window launches it (CTR_AUTORESET_POOLED: done "
-                                                         "envs copy their precomputed reset), %d back-to-back launches "
-                                                         "after the window, no refill among them; its frac prices the "
-                                                         "same FK work as kernel_ms" % (R_steps - 1)
-                                                         if k_ms_pooled else
-                                                         "not measured: the window's steps also run the per-step gather "
-                                                         "(or a refill period of one step)"),
-                     "flops_per_launch": flops_env_step, "sincos_per_launch": sincos,
-                     "nfev_per_env_step": nfev_mean,
-                     "bytes_per_launch_algorithmic": BYTES_STEP * n,
-                     "hbm_gbs_algorithmic": BYTES_STEP * n / (k_ms * 1e-3) / 1e9,
-                     "hbm_frac_algorithmic": BYTES_STEP * n / (k_ms * 1e-3) / 1e9 / PEAK_HBM,
-                     "note": ("bound is the FP64 vector pipe: no GEMM-shaped work for MFMA, far above the HBM ridge; "
-                              "peak = MI355X FP64 vector spec; flops from device counters (sincos not priced): " +
-                              ("the EXECUTED work of the rigid segment-power path (125 flop per segment map, 37 per "
-                               "W-polynomial composition, 63 per 3x4 composition of the 8-lane group product), not the "
-                               "stepped RK4 count"
-                               if cfgd["model"] == "rigid" else
-                               "SURVEY 8(d) count for the RK4 steps taken stage by stage (4 RHS x 102 + 252 per step); the "
-                               "tube-0-alone tail segments run as segment maps and are priced at their EXECUTED work (125 "
-                               "per map + 63 to apply it + 37 per composition), not at the stepped count"
-                               if cfgd["integrator"] == "rk4" else "SURVEY 8(d) count"))},
     }
-    tr = os.path.join(ROOT, "profiles", "traffic.json" if args.config == 3 else "traffic_c%d.json" % args.config)
-    if ws > 1:
-        # the one-GPU PMC passes do not see a rank's stores into its peers' rings (16 B per env and
-        # peer) nor RCCL's traffic
-        out["roofline"]["traffic"] = None
-        out["roofline"]["traffic_source"] = ("not measured for N > 1: profiles/traffic.json is k_step on one GPU "
-                                             "without the gather's peer stores")
-    elif os.path.exists(tr):
-        with open(tr) as fh:
-            t = json.load(fh)
-        if t.get("envs") == n and t.get("config", 3) == args.config and systems == [0]:
-            out["roofline"]["traffic"] = t.get("bytes_per_launch")
-            out["roofline"]["traffic_source"] = "profiles/%s: %s" % (os.path.basename(tr), t.get("note", ""))
-            out["roofline"]["traffic_over_algorithmic"] = t.get("bytes_per_launch") / (BYTES_STEP * n)
-            # the PMC passes run the window's pooled steps, so their bytes include the auto-resets at
-            # the window's rate: the algorithmic bytes of those resets beside them
-            if resets:
-                per_reset = BYTES_RESET + BYTES_RESET_WRITE_FIXED + 13 * (8 if args.obs_dtype == "float64" else 4)
-                alg_r = BYTES_STEP * n + per_reset * resets / args.steps
-                out["roofline"]["bytes_per_launch_algorithmic_with_resets"] = alg_r
-                out["roofline"]["bytes_per_reset_algorithmic"] = per_reset
-                out["roofline"]["traffic_over_algorithmic_with_resets"] = t.get("bytes_per_launch") / alg_r
-    if not args.no_cpu_baseline and ws == 1:
+    if args.full:
+        achieved_tf = flops_env_step / (k_ms * 1e-3) / 1e12
+        traffic, traffic_note = measured_traffic(n, cfgd, systems) if ws == 1 else (None, None)
+        out["roofline"] = {"bound": "valu", "achieved": achieved_tf, "peak": PEAK_FP64_VALU, "unit": "TFLOP/s",
+                           "frac": achieved_tf / PEAK_FP64_VALU, "traffic": traffic,
+                           "traffic_source": traffic_note,
+                           "kernel": "k_step", "kernel_ms": k_ms,
+                           "kernel_autoreset": "off (achieved / frac time k_step with CTR_AUTORESET_OFF: 32 back-to-back "
+                                               "launches from the window's joints, the FK work priced on those joints)",
+                           "kernel_ms_autoreset_pooled": k_ms_pooled,
+                           "frac_autoreset_pooled": (flops_env_step / (k_ms_pooled * 1e-3) / 1e12 / PEAK_FP64_VALU
+                                                     if k_ms_pooled else None),
+                           "kernel_ms_autoreset_pooled_note": ("k_step as the window launches it (CTR_AUTORESET_POOLED: done "
+                                                               "envs copy their precomputed reset), %d back-to-back launches "
+                                                               "after the window, no refill among them; its frac prices the "
+                                                               "same FK work as kernel_ms" % (R_steps - 1)
+                                                               if k_ms_pooled else
+                                                               "not measured: the window's steps also run the per-step gather "
+                                                               "(or a refill period of one step)"),
+                           "flops_per_launch": flops_env_step, "sincos_per_launch": sincos,
+                           "nfev_per_env_step": nfev_mean,
+                           "bytes_per_launch_algorithmic": BYTES_STEP * n,
+                           "hbm_gbs_algorithmic": BYTES_STEP * n / (k_ms * 1e-3) / 1e9,
+                           "hbm_frac_algorithmic": BYTES_STEP * n / (k_ms * 1e-3) / 1e9 / PEAK_HBM,
+                           "note": ("bound is the FP64 vector pipe: no GEMM-shaped work for MFMA, far above the HBM ridge; "
+                                    "peak = MI355X FP64 vector spec; flops from device counters (sincos not priced): " +
+                                    ("the EXECUTED work of the rigid segment-power path (125 flop per segment map, 37 per "
+                                     "W-polynomial composition, 63 per 3x4 composition of the 8-lane group product), not the "
+                                     "stepped RK4 count"
+                                     if cfgd["model"] == "rigid" else
+                                     "SURVEY 8(d) count for the RK4 steps taken stage by stage (4 RHS x 102 + 252 per step); the "
+                                     "tube-0-alone tail segments run as segment maps and are priced at their EXECUTED work (125 "
+                                     "per map + 63 to apply it + 37 per composition), not at the stepped count"
+                                     if cfgd["integrator"] == "rk4" else "SURVEY 8(d) count"))}
+        tr = os.path.join(ROOT, "profiles", "traffic.json" if args.config == 3 else "traffic_c%d.json" % args.config)
+        if ws > 1:
+            # the one-GPU PMC passes do not see a rank's stores into its peers' rings (16 B per env and
+            # peer) nor RCCL's traffic
+            out["roofline"]["traffic"] = None
+            out["roofline"]["traffic_source"] = ("not measured for N > 1: profiles/traffic.json is k_step on one GPU "
+                                                 "without the gather's peer stores")
+        elif os.path.exists(tr):
+            with open(tr) as fh:
+                t = json.load(fh)
+            if t.get("envs") == n and t.get("config", 3) == args.config and systems == [0]:
+                out["roofline"]["traffic"] = t.get("bytes_per_launch")
+                out["roofline"]["traffic_source"] = "profiles/%s: %s" % (os.path.basename(tr), t.get("note", ""))
+                out["roofline"]["traffic_over_algorithmic"] = t.get("bytes_per_launch") / (BYTES_STEP * n)
+                # the PMC passes run the window's pooled steps, so their bytes include the auto-resets at
+                # the window's rate: the algorithmic bytes of those resets beside them
+                if resets:
+                    per_reset = BYTES_RESET + BYTES_RESET_WRITE_FIXED + 13 * (8 if args.obs_dtype == "float64" else 4)
+                    alg_r = BYTES_STEP * n + per_reset * resets / args.steps
+                    out["roofline"]["bytes_per_launch_algorithmic_with_resets"] = alg_r
+                    out["roofline"]["bytes_per_reset_algorithmic"] = per_reset
+                    out["roofline"]["traffic_over_algorithmic_with_resets"] = t.get("bytes_per_launch") / alg_r
+    if args.full and not args.no_cpu_baseline and ws == 1:
         out["parity"] = parity_probe(env, cfgd)
         out["cpu_baseline"] = cpu_baseline(args, cfgd)
     print(json.dumps(out), flush=True)

@@ -51,21 +51,21 @@ suite)
     run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
     ;;
 bench)
-    run bench 300 python bench.py --gpus 1 --steps 20 --warmup 5
-    run bench_2 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline
-    TAILN=3 run bench_n2_gloo 300 env CTR_BENCH_BACKEND=gloo CTR_BENCH_SAME_DEVICE=1 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline
-    TAILN=3 run bench_c5_n2_gloo 300 env CTR_BENCH_BACKEND=gloo CTR_BENCH_SAME_DEVICE=1 python bench.py --gpus 2 --config 5 --steps 20 --warmup 5 --no-cpu-baseline
+    run bench 300 python bench.py --full --gpus 1 --steps 20 --warmup 5
+    run bench_2 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
+    TAILN=3 run bench_n2_gloo 300 env CTR_BENCH_BACKEND=gloo CTR_BENCH_SAME_DEVICE=1 python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline
+    TAILN=3 run bench_c5_n2_gloo 300 env CTR_BENCH_BACKEND=gloo CTR_BENCH_SAME_DEVICE=1 python bench.py --full --gpus 2 --config 5 --steps 20 --warmup 5 --no-cpu-baseline
     ;;
 evidence)
-    run bench 300 python bench.py --gpus 1 --steps 20 --warmup 5
-    run bench_2 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline
-    run bench_128 300 python bench.py --steps 128 --warmup 5 --no-cpu-baseline
-    run bench_obs64 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --obs-dtype float64
-    run bench_c2 300 python bench.py --config 2 --steps 20 --warmup 5 --cpu-seconds 5
-    run bench_c2b 300 python bench.py --config 2 --steps 20 --warmup 5 --no-cpu-baseline
-    run bench_c5 300 python bench.py --config 5 --steps 20 --warmup 5 --cpu-seconds 5
-    run bench_c5_128 300 python bench.py --config 5 --warmup 5 --no-cpu-baseline
-    run bench_mixed 300 python bench.py --systems 0,1,2,3 --steps 20 --warmup 5 --cpu-seconds 5
+    run bench 300 python bench.py --full --gpus 1 --steps 20 --warmup 5
+    run bench_2 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
+    run bench_128 300 python bench.py --full --steps 128 --warmup 5 --no-cpu-baseline
+    run bench_obs64 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --obs-dtype float64
+    run bench_c2 300 python bench.py --full --config 2 --steps 20 --warmup 5 --cpu-seconds 5
+    run bench_c2b 300 python bench.py --full --config 2 --steps 20 --warmup 5 --no-cpu-baseline
+    run bench_c5 300 python bench.py --full --config 5 --steps 20 --warmup 5 --cpu-seconds 5
+    run bench_c5_128 300 python bench.py --full --config 5 --warmup 5 --no-cpu-baseline
+    run bench_mixed 300 python bench.py --full --systems 0,1,2,3 --steps 20 --warmup 5 --cpu-seconds 5
     ;;
 soak)
     run soak_pool 600 python tools/soak_pool.py
@@ -82,7 +82,7 @@ profile)
     tail -3 gpurun_out/profile_${TAG:-r04}.log
     ;;
 traffic)
-    run bench_base 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline
+    run bench_base 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
     pmc r4t_fetch_b6 FETCH_SIZE --steps 20 --warmup 5 --profile-only
     pmc r4t_write_b6 WRITE_SIZE --steps 20 --warmup 5 --profile-only
     pmc r4t_fetch_b0 FETCH_SIZE --steps 20 --warmup 5 --profile-only --refill-budget 0
@@ -116,7 +116,7 @@ ab)
     for rep in 1 2; do
         for v in libctr_reach_amd.so $AB; do
             TAILN=3 run steps_${v}_$rep 200 env CTR_REACH_AMD_LIB=$LIBDIR/$v python tools/time_step_modes.py
-            run bench_${v}_$rep 300 env CTR_REACH_AMD_LIB=$LIBDIR/$v python bench.py --steps 20 --warmup 5 --no-cpu-baseline
+            run bench_${v}_$rep 300 env CTR_REACH_AMD_LIB=$LIBDIR/$v python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
         done
     done
     ;;

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
-    python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline $BA > $OUT/bench_under_trace.log 2>&1 || exit 1
+    python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline $BA > $OUT/bench_under_trace.log 2>&1 || exit 1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o run -- \
     python3 bench.py --steps 10 --warmup 2 --profile-only $BA > $OUT/pmc1.log 2>&1 || exit 2
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o run -- \

@@ -7,8 +7,9 @@
 * configs[4] (65 536 envs, compliant, RK4 at 400 steps/m) at full size: joint constraints and
   step outputs hold for the whole batch, and a 4 096-env subset of the last step matches the
   oracle (tips <= 1e-11 m, joints / reward bit-exact).
-* bench.py's steady-state window (staggered episodes, refills inside the window) and its
-  two-rank entry point (gloo rehearsal on one GPU).
+* bench.py's steady-state window (staggered episodes, refills inside the window), its plain line
+  and --dump-outputs (repeatable from run to run), the --full legs, and its two-rank entry point
+  (gloo rehearsal on one GPU).
 """
 import json
 import os
@@ -121,6 +122,47 @@ def test_bench_window_holds_steady_state_resets(cuda):
     # staggered clocks: about n / 150 time-limit resets per step, plus early successes
     expect = n * steps / 150.0
     assert 0.6 * expect < ss["resets_in_window"] < 3.0 * expect, ss
+
+
+def test_bench_plain_line_and_repeatable_dump(cuda, tmp_path):
+    """A plain run prints the headline line without the --full legs, and --dump-outputs writes the
+    last timed step's outputs: float32 / float64 arrays, one row per env, identical from run to run."""
+    n, steps = 4096, 6
+    args = ["--gpus", "1", "--envs", str(n), "--steps", str(steps), "--warmup", "1"]
+    outs = [_bench(args + ["--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    for out in outs:
+        assert out["steps"] == steps and out["ms_per_step"] > 0 and out["unit"] == "env-steps/s"
+        assert abs(out["value"] - n / (out["ms_per_step"] * 1e-3)) <= 1e-6 * out["value"]
+        assert "roofline" not in out and "parity" not in out and "cpu_baseline" not in out
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert {"observation.npy", "achieved_goal.npy", "desired_goal.npy", "reward.npy", "done.npy",
+            "is_success.npy", "joints.npy"} <= set(names)
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and a.shape[0] == n, name
+        np.testing.assert_array_equal(a, b, err_msg=name)
+        total += a.nbytes
+    assert total <= 64 * 1000 * 1000
+    ag, dg = np.load(tmp_path / "a" / "achieved_goal.npy"), np.load(tmp_path / "a" / "desired_goal.npy")
+    assert ag.dtype == np.float64 and np.isfinite(ag).all() and np.abs(ag).max() > 0
+    # the dumped step's own outputs are consistent: reward = -(distance > tol) for envs still running
+    live = np.load(tmp_path / "a" / "done.npy") == 0
+    err = np.load(tmp_path / "a" / "error.npy")
+    np.testing.assert_allclose(err[live], np.linalg.norm(ag[live] - dg[live], axis=1).astype(np.float32), rtol=1e-6)
+    live &= np.abs(err - 0.020) > 1e-6        # error is the float32 of the distance the reward compared
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "reward.npy")[live], -(err[live] > 0.020).astype(np.float32))
+
+
+def test_bench_full_adds_roofline_and_cpu_legs(cuda):
+    """--full brings the kernel roofline, the parity probe and the CPU baseline back; an odd
+    --steps (no captured graph fits) still times exactly that many steps."""
+    out = _bench(["--gpus", "1", "--envs", "4096", "--steps", "5", "--warmup", "1", "--full", "--cpu-seconds", "0.2"])
+    assert out["steps"] == 5 and out["config"]["launch"].startswith("per step")
+    assert out["roofline"]["kernel"] == "k_step" and out["roofline"]["kernel_ms"] > 0
+    assert out["parity"]["envs"] == 4096 and out["parity"]["tip_l2_max_m"] < 1e-9
+    assert out["cpu_baseline"]["value"] > 0
 
 
 def test_bench_two_ranks_gloo_rehearsal(cuda):
