@@ -7,6 +7,8 @@
 //                 success, error, observation; a done env takes its next reset from the
 //                 reset pool (a copy), or is queued for k_reset      (envs/ctr_reach_env.py:124-158);
 //                 rigid model + fixed-step RK4: one env per 8-lane group (fk_group_rigid4)
+//   k_step_many   the k steps of a refill period in one launch: the staging once, then k_step's
+//                 per-step code k times per wave, no inter-wave wait between the steps
 //   k_reset       CtrReachEnv.reset, TWO lanes per env (goal FK | start FK in parallel),
 //                 for the queued / masked envs                        (envs/ctr_reach_env.py:70-114)
 //   k_refill      precomputes queued resets into the pool, two lanes per reset
@@ -621,13 +623,24 @@ struct StepFlags {
     uint32_t pooled_r = 0;
 };
 
+// What an env's next step starts from besides its joints, as step_finish leaves it in the batch
+// rows (system, t, epoch, desired goal): k_step_many carries it to the next step of the launch
+// instead of reading the rows back.
+struct StepCarry {
+    int s;
+    int32_t t;
+    uint32_t ep;
+    double dg[3];
+};
+
 // t_prev, epoch, dg_prev: the env's clock, reset count and desired goal before the step (loaded
-// at the start of the step).
+// at the start of the step).  q: in, the joints after the action; out, the joints the step leaves
+// (a pooled reset's start joints).  nx: NULL, or gets the rest of the state the step leaves.
 __device__ __forceinline__ void step_finish(const KCfg &kc, const ctr_batch_t &b, const ctr_step_out_t &o, int64_t e,
                                             int s, float q[6], double ag[3], const FkStats &st, int32_t autoreset,
                                             StepFlags &fl, const ctr_her_t *her, const float *action,
                                             PoolPre &lp, int32_t t_prev, uint32_t epoch, const double dg_prev[3],
-                                            float4 &grow)
+                                            float4 &grow, StepCarry *nx = nullptr)
 {
     const int32_t t = t_prev + 1;
     double dg[3];
@@ -664,6 +677,7 @@ __device__ __forceinline__ void step_finish(const KCfg &kc, const ctr_batch_t &b
         her_record_lane(*her, e, action, reward, done, obf, ag, tol);
     }
     int32_t t_out = t;
+    if (nx) { nx->s = s; nx->ep = epoch; }
     if (autoreset && done) {
         if (o.terminal_obs) write_obs(o.terminal_obs, e, obs, multi, f64);
         if (o.terminal_achieved)
@@ -706,6 +720,7 @@ __device__ __forceinline__ void step_finish(const KCfg &kc, const ctr_batch_t &b
             fl.pooled = true;
             fl.pooled_r = r;
             t_out = 0;
+            if (nx) { nx->s = s2; nx->ep = r; }
         } else if (autoreset == CTR_AUTORESET_POOLED) {
             // the caller promised a full pool and launches no sweep: report, keep the env done
             // (it takes its reset on a later step, once a refill has precomputed it)
@@ -721,6 +736,11 @@ __device__ __forceinline__ void step_finish(const KCfg &kc, const ctr_batch_t &b
     for (int i = 0; i < 3; ++i) b.achieved_goal[3 * e + i] = ag[i];
     write_obs(o.obs, e, obs, multi, f64);
     if (o.status) o.status[e] = stat;
+    if (nx) {
+        nx->t = t_out;
+        #pragma unroll
+        for (int i = 0; i < 3; ++i) nx->dg[i] = dg[i];
+    }
 }
 
 // step_finish for the rigid 8-lane group path (no HER): the env's two observations -- of the
@@ -830,13 +850,13 @@ __device__ __forceinline__ void step_finish_group(const KCfg &kc, const ctr_batc
 // queue) and the fused push of the step's rows.
 __device__ __forceinline__ void step_epilogue(const ctr_batch_t &b, const ctr_step_out_t &o, int32_t autoreset,
                                               const StepFlags &fl, int64_t e, bool live, const ctr_gather_push_t *gp,
-                                              bool slot_free0, float4 grow)
+                                              bool slot_free0, float4 grow, bool zero_miss = true)
 {
     if (autoreset) {
         if (autoreset == CTR_AUTORESET_POOLED) {
             // no miss sweep follows: zero the next step's miss counter here (this step neither
-            // reads nor appends to either counter)
-            if (blockIdx.x == 0 && threadIdx.x == 0) b.work[(b.work_parity & 1) ^ 1] = 0;
+            // reads nor appends to either counter; k_step_many has zeroed them for all its steps)
+            if (zero_miss && blockIdx.x == 0 && threadIdx.x == 0) b.work[(b.work_parity & 1) ^ 1] = 0;
         } else {
             const int32_t one[1] = {(int32_t)e};
             wave_append(miss_counter(b), miss_items(b), b.n, fl.miss, one, 1);
@@ -862,10 +882,154 @@ __device__ __forceinline__ void step_epilogue(const ctr_batch_t &b, const ctr_st
     }
 }
 
+// The rows a step starts from: the env's state as the last step (or reset) left it, and the step's
+// action row.
+struct StepRows {
+    int s;
+    float q[6], a[6];
+    int32_t t;
+    uint32_t ep;
+    double dg[3];
+};
+
+// Issues the loads of row ec (unconditional, from a clamped row, so nothing waits for them before
+// the staging).
+__device__ __forceinline__ void step_rows_load(const ctr_batch_t &b, const float *__restrict__ actions, int64_t ec,
+                                               StepRows &r)
+{
+    r.s = b.system[ec];
+    #pragma unroll
+    for (int i = 0; i < 6; ++i) { r.q[i] = b.joints[6 * ec + i]; r.a[i] = actions[6 * ec + i]; }
+    r.t = b.t[ec];
+    r.ep = b.epoch[ec];
+    #pragma unroll
+    for (int i = 0; i < 3; ++i) r.dg[i] = b.desired_goal[3 * ec + i];
+}
+
+// k_step_many: where the next step's action row waits out the FK (one column per lane).
+__device__ __forceinline__ float (*next_action_lds())[BLOCK]
+{
+    __shared__ float s_next_a[6][BLOCK];
+    return s_next_a;
+}
+
+// One step of the workgroup's envs, after the staging (stage_load, stage_systems: s_sys, s_raw and
+// the trig table are in LDS) and with the step's rows loaded (r): the part k_step runs once and
+// k_step_many once per step of its period.  Nothing in it waits for another wave.
 // Torsionally rigid model with fixed-step RK4 (MODE bits 2 and 4): one env on a group of
 // SEG_GROUP lanes, whose segments run in parallel (fk_group_rigid4); other modes: one env per lane.
 // HER: record the step into the HER store (ctr_step_her); a compile-time switch, so the plain
 // step carries no trace of it (a runtime flag measured +2.3 us on k_step).
+// MANY (k_step_many; one env per lane, no HER, no gather): on return r holds the rows of the
+// env's next step -- the state step_finish left, carried instead of read back, and the row of
+// next_actions (NULL after the last step), whose load is issued before the FK and parked in LDS
+// across it (not in registers the FK loop would have to keep, like the finish's inputs).
+template <int MODE, bool HER, bool MANY>
+__device__ __forceinline__ void step_one(const KCfg &kc, const ctr_batch_t &b, const float *__restrict__ actions,
+                                         const ctr_step_out_t &o, int32_t autoreset, const ctr_her_t *her,
+                                         const SysK *s_sys, const ctr_tube_raw_t *s_raw, int64_t e, int j, bool in,
+                                         bool live, StepRows &r, const ctr_gather_push_t *gp, bool slot_free0,
+                                         const float *__restrict__ next_actions)
+{
+    constexpr bool GROUP = (MODE & 6) == 6;
+    static_assert(!MANY || (!GROUP && !HER), "k_step_many: one env per lane, no HER");
+    // one env per lane: the finish's inputs wait out the FK in LDS (they have landed during the
+    // staging), not in registers the FK loop would have to keep
+    __shared__ double s_fin_dg[3][BLOCK];
+    __shared__ int32_t s_fin_t[BLOCK];
+    __shared__ uint32_t s_fin_ep[BLOCK];
+    if constexpr (!GROUP) {
+        #pragma unroll
+        for (int i = 0; i < 3; ++i) s_fin_dg[i][threadIdx.x] = r.dg[i];
+        s_fin_t[threadIdx.x] = r.t;
+        s_fin_ep[threadIdx.x] = r.ep;
+    }
+    if constexpr (!MANY) {
+        // the step's sequence word after the packed rows (the copy-engine gather pushes it after them)
+        if (o.packed && o.packed_seq && blockIdx.x == 0 && threadIdx.x == 0)
+            *reinterpret_cast<uint4 *>(o.packed + 4 * b.n) = make_uint4(o.packed_seq, 0u, 0u, 0u);
+        // fused push gather: the previous gathered step's launch has completed, so its rows are in
+        // every rank's ring (performed at system scope); publish its sequence word there, and release
+        // this rank's slot of step gather_seq + 1 - depth (its readers ran before this launch)
+        if (blockIdx.x == 0) {
+            if (o.gather_prev) gather_publish_lane(o.gather_prev, o.gather_prev_seq);
+            if (gp) gather_release_lane(gp, o.gather_seq + 1u - (uint32_t)gp->depth);
+        }
+    }
+    StepFlags fl;
+    float4 grow = make_float4(0.f, 0.f, 0.f, 0.f);   // this lane's gather row (fused push)
+    if constexpr (GROUP) {
+        // every lane of the wave takes part in the group's shuffles
+        int s = 0;
+        float q[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        PoolPre pp;
+        // the env's next reset, in flight during set_action (lane 1 writes pooled resets without
+        // HER; the lead lane with it)
+        if (in && j == (HER ? 0 : 1)) pool_prefetch<true>(kc, b, e, autoreset, pp, r.t, r.ep);
+        if (in) {
+            s = clamp_sys(r.s, kc.c.n_systems);
+            #pragma unroll
+            for (int i = 0; i < 6; ++i) q[i] = r.q[i];
+            set_action_substeps(s_sys[s], kc.c.constrain_alpha != 0, kc.c.n_substeps, q, r.a);
+        }
+        const SysK &sy = in ? episode_sys(kc, s_sys, s_raw, s, b.epoch[e], (uint64_t)(b.env_base + e)) : s_sys[0];
+        const double qd[6] = {(double)q[0], (double)q[1], (double)q[2], (double)q[3], (double)q[4], (double)q[5]};
+        FkStats st = {0, 0, 0, 0, 0};
+        double ag[3];
+        if (fk_needs_careful_trig(qd))
+            fk_group_rigid4<(MODE & 1) != 0, true>(sy, qd, j, ag, st, (double)kc.c.rk4_steps_per_m);
+        else
+            fk_group_rigid4<(MODE & 1) != 0, false>(sy, qd, j, ag, st, (double)kc.c.rk4_steps_per_m);
+        if constexpr (HER) {
+            if (live)
+                step_finish(kc, b, o, e, s, q, ag, st, autoreset, fl, her, actions + 6 * e, pp, r.t, r.ep, r.dg, grow);
+        } else {
+            step_finish_group(kc, b, o, e, j, in, s, q, ag, st, autoreset, fl, pp, grow);
+        }
+    } else if (live) {
+        const int s = clamp_sys(r.s, kc.c.n_systems);
+        const SysK &sy = s_sys[s];
+        float q[6];
+        #pragma unroll
+        for (int i = 0; i < 6; ++i) q[i] = r.q[i];
+        // the next step's action row: its latency hides under set_action, its values wait out
+        // the FK in LDS (each lane reads back only its own column)
+        float a_nx[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if constexpr (MANY) {
+            if (next_actions)
+                #pragma unroll
+                for (int i = 0; i < 6; ++i) a_nx[i] = next_actions[6 * e + i];
+        }
+        PoolPre pp;
+        pool_prefetch(kc, b, e, autoreset, pp, r.t, r.ep);
+        set_action_substeps(sy, kc.c.constrain_alpha != 0, kc.c.n_substeps, q, r.a);
+        if constexpr (MANY) {
+            #pragma unroll
+            for (int i = 0; i < 6; ++i) next_action_lds()[i][threadIdx.x] = a_nx[i];
+        }
+        FkStats st = {0, 0, 0, 0, 0};
+        double ag[3];
+        fk_dispatch<MODE>(kc, episode_sys(kc, s_sys, s_raw, s, r.ep, (uint64_t)(b.env_base + e)), q, ag, st);
+        double dg_f[3];
+        #pragma unroll
+        for (int i = 0; i < 3; ++i) dg_f[i] = s_fin_dg[i][threadIdx.x];
+        StepCarry nx;
+        step_finish(kc, b, o, e, s, q, ag, st, autoreset, fl, her, MANY ? nullptr : actions + 6 * e, pp,
+                    s_fin_t[threadIdx.x], s_fin_ep[threadIdx.x], dg_f, grow, MANY ? &nx : nullptr);
+        if constexpr (MANY) {
+            r.s = nx.s;
+            r.t = nx.t;
+            r.ep = nx.ep;
+            #pragma unroll
+            for (int i = 0; i < 3; ++i) r.dg[i] = nx.dg[i];
+            #pragma unroll
+            for (int i = 0; i < 6; ++i) { r.q[i] = q[i]; r.a[i] = next_action_lds()[i][threadIdx.x]; }
+        }
+    }
+    step_epilogue(b, o, autoreset, fl, e, live, gp, slot_free0, grow, !MANY);
+}
+
+// k_step / k_step_her: the staging, then one step.
 template <int MODE, bool HER>
 __device__ __forceinline__ void step_body(const KCfg &kc, const ctr_batch_t &b, const float *__restrict__ actions,
                                           const ctr_step_out_t &o, int32_t autoreset, const HerK &hk)
@@ -886,91 +1050,47 @@ __device__ __forceinline__ void step_body(const KCfg &kc, const ctr_batch_t &b, 
     StageRegs stg;
     stage_load(kc, stg);
     __builtin_amdgcn_sched_barrier(0);       // keep the table loads ahead of the row loads
-    const int64_t ec = in ? e : b.n - 1;
-    const int s_in = b.system[ec];
-    float q_in[6], a_in[6];
-    #pragma unroll
-    for (int i = 0; i < 6; ++i) { q_in[i] = b.joints[6 * ec + i]; a_in[i] = actions[6 * ec + i]; }
-    const int32_t t_in = b.t[ec];
-    const uint32_t ep_in = b.epoch[ec];
-    double dg_in[3];
-    #pragma unroll
-    for (int i = 0; i < 3; ++i) dg_in[i] = b.desired_goal[3 * ec + i];
+    StepRows r;
+    step_rows_load(b, actions, in ? e : b.n - 1, r);
     // fused push: the consumers' release words, read behind the staging (checked after it)
     const ctr_gather_push_t *gp = o.gather;
     const uint32_t rel0 = gp ? gather_release_load(gp, o.gather_seq) : 0u;
     stage_systems<!GROUP>(kc, s_sys, s_raw, &stg);
     const bool slot_free0 = gp ? gather_slot_free(gp, o.gather_seq, rel0) : true;
-    // one env per lane: the finish's inputs wait out the FK in LDS (they have landed during the
-    // staging), not in registers the FK loop would have to keep
-    __shared__ double s_fin_dg[3][BLOCK];
-    __shared__ int32_t s_fin_t[BLOCK];
-    __shared__ uint32_t s_fin_ep[BLOCK];
-    if constexpr (!GROUP) {
-        #pragma unroll
-        for (int i = 0; i < 3; ++i) s_fin_dg[i][threadIdx.x] = dg_in[i];
-        s_fin_t[threadIdx.x] = t_in;
-        s_fin_ep[threadIdx.x] = ep_in;
+    step_one<MODE, HER, false>(kc, b, actions, o, autoreset, her, s_sys, s_raw, e, j, in, live, r, gp, slot_free0,
+                               nullptr);
+}
+
+// k_step_many: the staging once, then the k steps of the period, each wave on its own 64 envs
+// from the first step to the last.  A step of an env reads only what the env's own lane wrote in
+// the step before (carried in registers) and its action row, so nothing orders the waves after
+// the staging barrier: no barrier, flag or other inter-wave wait in the loop.
+template <int MODE>
+__device__ __forceinline__ void step_body_many(const KCfg &kc, const ctr_batch_t &b, const ctr_action_seq_t &seq,
+                                               int32_t k, const ctr_step_out_t &o, int32_t autoreset)
+{
+    __shared__ SysK s_sys[CTR_MAX_SYSTEMS];
+    __shared__ ctr_tube_raw_t s_raw[CTR_MAX_SYSTEMS];
+    const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool live = e < b.n;
+    StageRegs stg;
+    stage_load(kc, stg);
+    __builtin_amdgcn_sched_barrier(0);       // keep the table loads ahead of the row loads
+    StepRows r;
+    step_rows_load(b, seq.a[0], live ? e : b.n - 1, r);
+    stage_systems<true>(kc, s_sys, s_raw, &stg);
+    // CTR_AUTORESET_POOLED: no step of the period appends to either miss counter; zero what the k
+    // steps would have zeroed one by one (the other parity's, and from the second step on this one's)
+    if (autoreset == CTR_AUTORESET_POOLED && blockIdx.x == 0 && threadIdx.x == 0) {
+        b.work[(b.work_parity & 1) ^ 1] = 0;
+        if (k > 1) b.work[b.work_parity & 1] = 0;
     }
-    // the step's sequence word after the packed rows (the copy-engine gather pushes it after them)
-    if (o.packed && o.packed_seq && blockIdx.x == 0 && threadIdx.x == 0)
-        *reinterpret_cast<uint4 *>(o.packed + 4 * b.n) = make_uint4(o.packed_seq, 0u, 0u, 0u);
-    // fused push gather: the previous gathered step's launch has completed, so its rows are in
-    // every rank's ring (performed at system scope); publish its sequence word there, and release
-    // this rank's slot of step gather_seq + 1 - depth (its readers ran before this launch)
-    if (blockIdx.x == 0) {
-        if (o.gather_prev) gather_publish_lane(o.gather_prev, o.gather_prev_seq);
-        if (gp) gather_release_lane(gp, o.gather_seq + 1u - (uint32_t)gp->depth);
+    #pragma unroll 1
+    for (int32_t i = 0; i < k; ++i) {
+        const float *nxt = i + 1 < k ? seq.a[i + 1] : nullptr;
+        step_one<MODE, false, true>(kc, b, nullptr, o, autoreset, nullptr, s_sys, s_raw, e, 0, live, live, r, nullptr,
+                                    true, nxt);
     }
-    StepFlags fl;
-    float4 grow = make_float4(0.f, 0.f, 0.f, 0.f);   // this lane's gather row (fused push)
-    if constexpr (GROUP) {
-        // every lane of the wave takes part in the group's shuffles
-        int s = 0;
-        float q[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        PoolPre pp;
-        // the env's next reset, in flight during set_action (lane 1 writes pooled resets without
-        // HER; the lead lane with it)
-        if (in && j == (HER ? 0 : 1)) pool_prefetch<true>(kc, b, e, autoreset, pp, t_in, ep_in);
-        if (in) {
-            s = clamp_sys(s_in, kc.c.n_systems);
-            #pragma unroll
-            for (int i = 0; i < 6; ++i) q[i] = q_in[i];
-            set_action_substeps(s_sys[s], kc.c.constrain_alpha != 0, kc.c.n_substeps, q, a_in);
-        }
-        const SysK &sy = in ? episode_sys(kc, s_sys, s_raw, s, b.epoch[e], (uint64_t)(b.env_base + e)) : s_sys[0];
-        const double qd[6] = {(double)q[0], (double)q[1], (double)q[2], (double)q[3], (double)q[4], (double)q[5]};
-        FkStats st = {0, 0, 0, 0, 0};
-        double ag[3];
-        if (fk_needs_careful_trig(qd))
-            fk_group_rigid4<(MODE & 1) != 0, true>(sy, qd, j, ag, st, (double)kc.c.rk4_steps_per_m);
-        else
-            fk_group_rigid4<(MODE & 1) != 0, false>(sy, qd, j, ag, st, (double)kc.c.rk4_steps_per_m);
-        if constexpr (HER) {
-            if (live)
-                step_finish(kc, b, o, e, s, q, ag, st, autoreset, fl, her, actions + 6 * e, pp, t_in, ep_in, dg_in, grow);
-        } else {
-            step_finish_group(kc, b, o, e, j, in, s, q, ag, st, autoreset, fl, pp, grow);
-        }
-    } else if (live) {
-        const int s = clamp_sys(s_in, kc.c.n_systems);
-        const SysK &sy = s_sys[s];
-        float q[6];
-        #pragma unroll
-        for (int i = 0; i < 6; ++i) q[i] = q_in[i];
-        PoolPre pp;
-        pool_prefetch(kc, b, e, autoreset, pp, t_in, ep_in);
-        set_action_substeps(sy, kc.c.constrain_alpha != 0, kc.c.n_substeps, q, a_in);
-        FkStats st = {0, 0, 0, 0, 0};
-        double ag[3];
-        fk_dispatch<MODE>(kc, episode_sys(kc, s_sys, s_raw, s, ep_in, (uint64_t)(b.env_base + e)), q, ag, st);
-        double dg_f[3];
-        #pragma unroll
-        for (int i = 0; i < 3; ++i) dg_f[i] = s_fin_dg[i][threadIdx.x];
-        step_finish(kc, b, o, e, s, q, ag, st, autoreset, fl, her, actions + 6 * e, pp, s_fin_t[threadIdx.x],
-                    s_fin_ep[threadIdx.x], dg_f, grow);
-    }
-    step_epilogue(b, o, autoreset, fl, e, live, gp, slot_free0, grow);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1164,6 +1284,14 @@ __global__ __launch_bounds__(step_block<MODE>()) void k_step_her(KCfg kc, ctr_ba
 {
     if constexpr (pair_mode<MODE>()) step_body_pair<MODE, true>(kc, b, actions, o, autoreset, hk);
     else step_body<MODE, true>(kc, b, actions, o, autoreset, hk);
+}
+
+// The k steps of a period in one launch (ctr_step_many): one env per lane only.
+template <int MODE>
+__global__ __launch_bounds__(BLOCK) void k_step_many(KCfg kc, ctr_batch_t b, ctr_action_seq_t seq, int32_t k,
+                                                     ctr_step_out_t o, int32_t autoreset)
+{
+    if constexpr (!pair_mode<MODE>() && (MODE & 6) != 6) step_body_many<MODE>(kc, b, seq, k, o, autoreset);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1934,6 +2062,50 @@ int ctr_step(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const float 
              int32_t autoreset, void *stream)
 {
     return step_launch(cfg, batch, actions, out, autoreset, nullptr, stream);
+}
+
+int ctr_step_many(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_action_seq_t *actions, int32_t k,
+                  const ctr_step_out_t *out, int32_t autoreset, void *stream)
+{
+    if (int r = check_cfg(cfg)) return r;
+    if (!batch || !out || !actions) return fail(CTR_EINVAL, "ctr_step_many: NULL argument");
+    if (k < 1 || k > CTR_STEP_MANY_MAX) return fail(CTR_EINVAL, "ctr_step_many: k must be in 1..CTR_STEP_MANY_MAX (64)");
+    for (int32_t i = 0; i < k; ++i)
+        if (!actions->a[i]) return fail(CTR_EINVAL, "ctr_step_many: NULL action buffer among a[0..k-1]");
+    const ctr_batch_t b = *batch;
+    const ctr_step_out_t o = *out;
+    if (int r = check_batch(b, "ctr_step_many: batch buffer missing")) return r;
+    if (autoreset != CTR_AUTORESET_OFF && autoreset != CTR_AUTORESET_POOLED)
+        return fail(CTR_EINVAL, "ctr_step_many: autoreset must be CTR_AUTORESET_OFF or CTR_AUTORESET_POOLED (a miss sweep "
+                                "is a launch between two steps)");
+    if (o.packed || o.gather || o.gather_prev)
+        return fail(CTR_EINVAL, "ctr_step_many: not with packed rows or the push gather (out->packed, gather, gather_prev)");
+    const KCfg kc = make_kcfg(cfg);
+    if (pair_mode<2>() && kc.mode == 2)
+        return fail(CTR_EINVAL, "ctr_step_many: not for the lane-pair step (compliant model, fixed-step RK4)");
+    if ((kc.mode & 6) == 6)
+        return fail(CTR_EINVAL, "ctr_step_many: not for the 8-lane group step (rigid model, fixed-step RK4)");
+    if (pair_mode<0>() && kc.mode == 0) return fail(CTR_EINVAL, "ctr_step_many: not for the lane-pair step");
+    if (b.n == 0) return 0;
+    if (!o.obs || !o.reward || !o.done || !o.success || !o.error) return fail(CTR_EINVAL, "ctr_step_many: output missing");
+    if (autoreset && !b.work) return fail(CTR_EINVAL, "ctr_step_many: autoreset needs batch->work");
+    if (autoreset == CTR_AUTORESET_POOLED && b.pool_depth <= 0)
+        return fail(CTR_EINVAL, "ctr_step_many: CTR_AUTORESET_POOLED needs a reset pool");
+    if (b.pool_depth > 0 && !cfg->resample_joints) return fail(CTR_EINVAL, "the reset pool needs resample_joints");
+    ctr_action_seq_t seq;                        // by value into the kernel arguments
+    for (int32_t i = 0; i < CTR_STEP_MANY_MAX; ++i) seq.a[i] = i < k ? actions->a[i] : nullptr;
+    const dim3 g(grid_for(b.n)), blk(BLOCK);
+    const size_t shm = lane_lds_bytes(kc);
+    hipStream_t s = (hipStream_t)stream;
+    switch (kc.mode) {
+    case 0: hipLaunchKernelGGL(k_step_many<0>, g, blk, shm, s, kc, b, seq, k, o, autoreset); break;
+    case 1: hipLaunchKernelGGL(k_step_many<1>, g, blk, shm, s, kc, b, seq, k, o, autoreset); break;
+    case 2: hipLaunchKernelGGL(k_step_many<2>, g, blk, shm, s, kc, b, seq, k, o, autoreset); break;
+    case 3: hipLaunchKernelGGL(k_step_many<3>, g, blk, shm, s, kc, b, seq, k, o, autoreset); break;
+    case 4: hipLaunchKernelGGL(k_step_many<4>, g, blk, shm, s, kc, b, seq, k, o, autoreset); break;
+    default: hipLaunchKernelGGL(k_step_many<5>, g, blk, shm, s, kc, b, seq, k, o, autoreset); break;
+    }
+    return hip_check("ctr_step_many launch");
 }
 
 int ctr_reset(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const uint8_t *mask, const double *goal,

@@ -16,6 +16,8 @@ Semantics per environment follow CtrReachEnv (envs/ctr_reach_env.py:13-210):
 Random draws come from a Philox4x32-10 stream keyed by (seed, global env id, reset number),
 so results do not depend on how environments are sharded over GPUs.
 """
+import os
+
 import numpy as np
 
 from . import _abi
@@ -96,7 +98,8 @@ class CtrReachVecEnv(object):
 
     def __init__(self, num_envs, device="cuda", seed=0, env_base=0, autoreset=True, record_info=True,
                  pool_depth=None, refill_interval=64, integrator="rk45_scipy", rk4_steps_per_m=100,
-                 model="compliant", pack_outputs=False, obs_dtype="float32", refill_budget=None, **kwargs):
+                 model="compliant", pack_outputs=False, obs_dtype="float32", refill_budget=None, fused_period=True,
+                 **kwargs):
         torch = _torch()
         kw = default_kwargs()
         kw.update(kwargs)
@@ -173,6 +176,10 @@ class CtrReachVecEnv(object):
         self.gather_seq = 0       # fused push: the last step pushed
         self.refills = 0          # ctr_pool_refill launches so far (bench accounting)
         self.sweeps = 0           # steps that launched the auto-reset miss sweep (CTR_AUTORESET_SWEEP)
+        # capture_steps runs each refill period as one ctr_step_many launch where step_many can
+        # (fused_period=False or CTR_FUSED_PERIOD=0: one launch per step, for A/B runs)
+        self.fused_period = bool(fused_period) and os.environ.get("CTR_FUSED_PERIOD", "1") != "0"
+        self.fused_launches = 0   # ctr_step_many launches so far
         # reset pool: resets are a pure function of (seed, env id, reset number), so they are
         # precomputed in batches every `refill_interval` steps and consumed by a copy
         # depth >= the refill interval: every env then finds its next reset in the pool on every
@@ -425,10 +432,76 @@ class CtrReachVecEnv(object):
             if self._steps_since_refill >= self.refill_interval:
                 self.refill_pool(stream)
 
+    def step_many_ineligible(self):
+        """None if step_many can run this env's steps, else the reason it cannot."""
+        if self._her is not None:
+            return "not with the HER feed"
+        if self._push_gather is not None or self.packed_bufs is not None:
+            return "not with packed outputs or the push gather"
+        if self.integrator == "rk4":
+            if self.model == "rigid":
+                return "not for the rigid model's fixed-step RK4 (8-lane group step)"
+            uy = any(self.cfg.systems[s].Uy[i] != 0.0 for s in range(self.n_systems) for i in range(3))
+            if not uy:
+                return "not for the compliant model's fixed-step RK4 (lane-pair step)"
+        if self.autoreset and not (self.pool_depth and self._pool_full):
+            return "auto-reset needs the reset pool, full (every reset of the steps precomputed)"
+        return None
+
+    def step_many(self, actions, stream=None):
+        """len(actions) consecutive step_raw calls, each refill period's steps as one launch
+        (ctr_step_many: a wave takes its envs through the period's steps without the device-wide
+        join between two launches).  The state, the outputs and the host bookkeeping afterwards are
+        those of the step_raw calls, bit for bit; a launch never runs past a refill boundary (it
+        ends there, the refill follows, the next launch takes the next period) or past
+        CTR_STEP_MANY_MAX steps.  actions: [N, 6] float32 contiguous device tensors, which must
+        stay alive until the launches have run.  Raises RuntimeError where the steps need more
+        than this launch gives (step_many_ineligible): HER, packed outputs or the push gather, the
+        lane-pair and 8-lane group modes, auto-reset without a full pool."""
+        torch = _torch()
+        why = self.step_many_ineligible()
+        if why:
+            raise RuntimeError("step_many: " + why)
+        actions = list(actions)
+        for a in actions:
+            if (a.dtype != torch.float32 or a.device != self.device or not a.is_contiguous()
+                    or a.shape != (self.num_envs, 6)):
+                raise ValueError("step_many: actions must be contiguous float32 [%d, 6] tensors on %s"
+                                 % (self.num_envs, self.device))
+        sp = _abi.stream_ptr(stream, self.device.index)
+        i = 0
+        while i < len(actions):
+            k = min(len(actions) - i, _abi.CTR_STEP_MANY_MAX)
+            if self.pool_depth:                # never past the refill that falls due
+                k = min(k, self.refill_interval - self._steps_since_refill)
+            mode = _abi.AUTORESET_OFF
+            if self.autoreset:                 # every step of the launch as step_raw would run it: POOLED
+                k = min(k, self._pooled_steps() - self._steps_since_refill)
+                if k < 1 or not self._pool_full:
+                    raise RuntimeError("step_many: the next step's resets are not all in the pool")
+                mode = _abi.AUTORESET_POOLED
+            seq = _abi.CtrActionSeq()
+            for j in range(k):
+                seq.a[j] = actions[i + j].data_ptr()
+            rc = self.lib.ctr_step_many(self.cfg, self._batch, seq, k, self._out, mode, sp)
+            _abi.check(rc, "ctr_step_many")
+            self.fused_launches += 1
+            if self.autoreset and k % 2:
+                self._batch.work_parity ^= 1
+            if self.pool_depth:
+                self._steps_since_refill += k
+                if self._steps_since_refill >= self.refill_interval:
+                    self.refill_pool(stream)
+            i += k
+
     def capture_steps(self, actions, stream=None):
         """Capture len(actions) consecutive steps (step_raw, with the pool refills that fall due)
         into one HIP graph; ``StepGraph.replay()`` then runs them with a single launch, so a
         launch-bound batch (configs[1]: 4 096 envs, ~10 us kernels) is not paced by the host.
+        Where step_many can run the env (and fused_period is on), each refill period is captured as
+        one ctr_step_many launch and its refill instead of refill_interval launches.  That capture
+        checks the action tensors as step_many does (contiguous float32 [N, 6] on the env's device,
+        else ValueError); the step-by-step capture takes their pointers unchecked, like step_raw.
 
         The host side of a step (buffer parities, the refill schedule, the auto-reset mode) is
         fixed in the graph, so the sequence must bring it back to where it started: start right
@@ -693,19 +766,26 @@ class StepGraph(object):
         self.actions = [a for a in actions]
         self.stream = stream if stream is not None else torch.cuda.Stream(device=env.device)
         self.stream.wait_stream(torch.cuda.current_stream(env.device))
-        refills, sweeps, seq = env.refills, env.sweeps, env.packed_seq
+        refills, sweeps, seq, fused = env.refills, env.sweeps, env.packed_seq, env.fused_launches
+        # each refill period as one launch (step_many) where the env allows it
+        self.fused = env.fused_period and env.step_many_ineligible() is None
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, stream=self.stream):
-            for a in self.actions:
-                env.step_raw(a, self.stream)
+            if self.fused:
+                env.step_many(self.actions, self.stream)
+            else:
+                for a in self.actions:
+                    env.step_raw(a, self.stream)
         self.refills_per_replay = env.refills - refills
+        self.fused_per_replay = env.fused_launches - fused
         # the capture launched nothing: its host bookkeeping is undone, replay() redoes it
-        env.refills, env.sweeps, env.packed_seq = refills, sweeps, seq
+        env.refills, env.sweeps, env.packed_seq, env.fused_launches = refills, sweeps, seq, fused
         assert env._steps_since_refill == 0 or not env.pool_depth
 
     def replay(self):
         """Run the captured steps (stream-ordered on the current stream, like step())."""
         self.graph.replay()
         self.env.refills += self.refills_per_replay
+        self.env.fused_launches += self.fused_per_replay
         if self.env.packed_bufs is not None:
             self.env.packed_seq += self.steps

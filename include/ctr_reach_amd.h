@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define CTR_ABI_VERSION 15
+#define CTR_ABI_VERSION 16
 #define CTR_MAX_SYSTEMS 8
 #define CTR_POOL_MAX 192          /* ctr_batch_t.pool_depth limit (reset slots per environment) */
 #define CTR_EINVAL (-1)
@@ -381,6 +381,30 @@ int ctr_set_action(const ctr_env_config_t *cfg, float *joints, const int32_t *sy
  * semantics) and their pre-reset observation goes to out->terminal_obs. */
 int ctr_step(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const float *actions,
              const ctr_step_out_t *out, int32_t autoreset, void *stream);
+
+/* k consecutive ctr_step calls in one launch (ABI 16): afterwards the batch state and the output
+ * buffers are exactly what ctr_step with actions->a[0], ..., actions->a[k - 1] (each [n][6] f32,
+ * device), the same autoreset and batch->work_parity toggled after every step would have left
+ * (terminal_obs / terminal_achieved: the rows of every step an env was done in, the last such
+ * step winning; the other outputs: the last step's).  One kernel runs the period: the tables are
+ * staged once and each wave takes its 64 environments through all k steps, with no device-wide
+ * join between the steps (a step of an environment reads only that environment's own state and
+ * its action row; the refill queue is append-only).  The entries of the queue may come in another
+ * order than k launches leave them; ctr_pool_refill's result does not depend on it.
+ * The pointer table is copied into the kernel arguments at the call: the caller's struct need not
+ * outlive it.  Nothing is allocated; stream-ordered like ctr_step.
+ * Supported: the one-environment-per-lane modes (every mode but the rigid model's fixed-step RK4,
+ * which runs on 8-lane groups, and the compliant model's fixed-step RK4 without y pre-curvature,
+ * which runs on lane pairs), autoreset CTR_AUTORESET_OFF or CTR_AUTORESET_POOLED, and
+ * out->packed, out->gather, out->gather_prev all NULL.  Anything else, k outside
+ * 1..CTR_STEP_MANY_MAX or a NULL entry in a[0..k-1] is CTR_EINVAL, before any HIP call.
+ * The caller keeps CTR_AUTORESET_POOLED's promise for all k steps (no refill falls inside). */
+#define CTR_STEP_MANY_MAX 64
+typedef struct ctr_action_seq_t {
+    const float *a[CTR_STEP_MANY_MAX];
+} ctr_action_seq_t;
+int ctr_step_many(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_action_seq_t *actions,
+                  int32_t k, const ctr_step_out_t *out, int32_t autoreset, void *stream);
 
 /* CtrReachEnv.reset for the environments with mask[i] != 0 (mask NULL = all).
  * goal [n][3] or NULL (sample a goal), system [n] or NULL (sample uniformly).
