@@ -186,13 +186,7 @@ __device__ __forceinline__ const SysK &episode_sys_at(const KCfg &kc, const SysK
 __device__ __forceinline__ const SysK &episode_sys(const KCfg &kc, const SysK *s_sys, const ctr_tube_raw_t *s_raw,
                                                    int s, uint32_t epoch, uint64_t genv)
 {
-    if (kc.c.domain_rand == 0.0 || epoch == 0) return s_sys[s];
-    SysK &me = s_lane_dyn[threadIdx.x];
-    domain_system(s_sys[s], s_raw[s], kc.c.domain_rand, kc.c.seed, epoch, genv, me, nullptr);
-    #pragma unroll
-    for (int j = 0; j < 11; ++j) sysk_derive(me, j);
-    me.lut = nullptr;
-    return me;
+    return episode_sys_at(kc, s_sys, s_raw, s, epoch, genv, (int)threadIdx.x);
 }
 
 // MODE bits: 1 = some tube has y pre-curvature, 2 = fixed-step RK4 (else scipy RK45),
@@ -1105,14 +1099,8 @@ __device__ __forceinline__ void step_body_many(const KCfg &kc, const ctr_batch_t
 #ifndef CTR_RK4_PAIR
 #define CTR_RK4_PAIR 1
 #endif
-// The headline (MODE 0, scipy RK45) on lane pairs (fk_pair_rk45): an A/B experiment, off in the
-// product build.  Measured 92.5-95.5 us against 72.3 us one env per lane (VERDICT r5 item 4,
-// DESIGN.md 3 "RK45 on lane pairs", profiles/r06_rk45pair_ab.txt); built by tools/experiments/ab_rk45pair.sh.
-#ifndef CTR_RK45_PAIR
-#define CTR_RK45_PAIR 0
-#endif
 template <int MODE>
-constexpr bool pair_mode() { return (CTR_RK4_PAIR && MODE == 2) || (CTR_RK45_PAIR && MODE == 0); }
+constexpr bool pair_mode() { return CTR_RK4_PAIR && MODE == 2; }
 template <int MODE>
 constexpr int step_block() { return pair_mode<MODE>() ? 2 * BLOCK : BLOCK; }
 template <int MODE>
@@ -1126,23 +1114,6 @@ __device__ __forceinline__ int pair_work_bucket(const ctr_system_t &sy, const fl
     const double e2 = fmax(0.0, (double)q[2] + sy.L[2]);
     const double e1 = fmax(e2, (double)q[1] + sy.L[1]);
     const double w = (4.0 * e2 + 3.0 * (e1 - e2)) * inv_wmax;     // in [0, 1] for nested tubes
-    return 255 - (int)fmin(fmax(w * 255.0, 0.0), 255.0);
-}
-
-// scipy RK45 (the CTR_RK45_PAIR experiment): the attempts follow the segment count (each gap
-// restarts the solver), so the key is the number of segment ends beyond s = 0 (the tubes'
-// curvature starts and tips: correlation 0.88 with the oracle's RHS count, the extension key
-// alone 0.68), the extension key breaking ties
-__device__ __forceinline__ int pair_work_bucket_rk45(const ctr_system_t &sy, const float q[6], double inv_wmax)
-{
-    int nsa = 0;
-    #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const double tipi = (double)q[i] + sy.L[i];
-        nsa += (tipi > 0.0) + (tipi - sy.Lc[i] > 0.0);
-    }
-    const int ext = 255 - pair_work_bucket(sy, q, inv_wmax);                   // 0 .. 255
-    const double w = ((double)nsa + 0.9 * (double)ext * (1.0 / 255.0)) * (1.0 / 7.0);
     return 255 - (int)fmin(fmax(w * 255.0, 0.0), 255.0);
 }
 
@@ -1190,12 +1161,7 @@ __device__ __forceinline__ void step_body_pair(const KCfg &kc, const ctr_batch_t
     // its bucket (in atomic order: the deal, not any result, depends on it) -- then its prefix sums
     double lmax = 0.0;
     for (int k = 0; k < kc.c.n_systems; ++k) lmax = fmax(lmax, s_sys[k].L[1]);
-#if defined(CTR_RK45_KEY_NSEG)
-    const int bkt = !in_n ? 255 : MODE == 0 ? pair_work_bucket_rk45(s_sys[sn], q, 1.0 / (4.0 * lmax))
-                                            : pair_work_bucket(s_sys[sn], q, 1.0 / (4.0 * lmax));
-#else
     const int bkt = in_n ? pair_work_bucket(s_sys[sn], q, 1.0 / (4.0 * lmax)) : 255;
-#endif
     int place = 0;
     if (!odd) {
         place = atomicAdd(&s_hist[bkt], 1);
@@ -1220,14 +1186,7 @@ __device__ __forceinline__ void step_body_pair(const KCfg &kc, const ctr_batch_t
     __syncthreads();
     const int rank = s_hist[bkt] + place;
     const int chunk = rank >> 5;
-#if defined(CTR_PAIR_DEAL_ADJ)          // A/B diagnostic: pair chunks onto waves 2k, 2k + 1 instead
-    const int slot = (chunk < 4 ? 2 * chunk : 2 * (7 - chunk) + 1) * 32 + (rank & 31);
-#elif defined(CTR_PAIR_NOSORT)          // A/B diagnostic: the natural env order
-    const int slot = pr;
-    (void)chunk;
-#else
     const int slot = (chunk < 4 ? chunk : 11 - chunk) * 32 + (rank & 31);
-#endif
     if (!odd) s_src[slot] = (uint16_t)pr;
     __syncthreads();
     const int src = s_src[pr];
@@ -1244,18 +1203,13 @@ __device__ __forceinline__ void step_body_pair(const KCfg &kc, const ctr_batch_t
     float4 grow = make_float4(0.f, 0.f, 0.f, 0.f);
     PoolPre pp;
     // the time-limit resets' rows in flight during the FK (the others load theirs when done)
-    if (MODE != 0 && in && j == (HER ? 0 : 1)) pool_prefetch(kc, b, e, autoreset, pp, t_in, ep_in);
+    if (in && j == (HER ? 0 : 1)) pool_prefetch(kc, b, e, autoreset, pp, t_in, ep_in);
     const SysK &sy = in ? episode_sys_at(kc, s_sys, s_raw, s, ep_in, (uint64_t)(b.env_base + e), pr) : s_sys[0];
     const double qd[6] = {(double)q[0], (double)q[1], (double)q[2], (double)q[3], (double)q[4], (double)q[5]};
     FkStats st = {0, 0, 0, 0, 0};
     double ag[3];
-    if constexpr (MODE == 0) {
-        if (fk_needs_careful_trig(qd)) fk_pair_rk45<true>(sy, qd, odd, ag, st);
-        else fk_pair_rk45<false>(sy, qd, odd, ag, st);
-    } else {
-        if (fk_needs_careful_trig(qd)) fk_pair_rk4<true>(sy, qd, odd, ag, st, (double)kc.c.rk4_steps_per_m);
-        else fk_pair_rk4<false>(sy, qd, odd, ag, st, (double)kc.c.rk4_steps_per_m);
-    }
+    if (fk_needs_careful_trig(qd)) fk_pair_rk4<true>(sy, qd, odd, ag, st, (double)kc.c.rk4_steps_per_m);
+    else fk_pair_rk4<false>(sy, qd, odd, ag, st, (double)kc.c.rk4_steps_per_m);
     if constexpr (HER) {
         if (live) {
             double dg_in[3];
@@ -2025,6 +1979,9 @@ int step_launch(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const flo
     HerK hk = {};
     if (her) hk.h = *her;
     const int32_t her_on = her != nullptr;
+    // (the mode 0 arm is never taken: pair_mode<0>() is false.  It stays because the kernels are
+    // emitted in the order this function first names them, and without it k_step<0> and
+    // k_step_her<0> move behind the MODE 2 pair in the code object)
     if ((kc.mode == 2 && pair_mode<2>()) || (kc.mode == 0 && pair_mode<0>())) {
         // configs[4]: 256 envs per 512-lane workgroup (step_body_pair); dynamic LDS: one domain table per env
         const dim3 g((unsigned)((b.n + BLOCK - 1) / BLOCK)), blk(2 * BLOCK);
@@ -2085,7 +2042,6 @@ int ctr_step_many(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const c
         return fail(CTR_EINVAL, "ctr_step_many: not for the lane-pair step (compliant model, fixed-step RK4)");
     if ((kc.mode & 6) == 6)
         return fail(CTR_EINVAL, "ctr_step_many: not for the 8-lane group step (rigid model, fixed-step RK4)");
-    if (pair_mode<0>() && kc.mode == 0) return fail(CTR_EINVAL, "ctr_step_many: not for the lane-pair step");
     if (b.n == 0) return 0;
     if (!o.obs || !o.reward || !o.done || !o.success || !o.error) return fail(CTR_EINVAL, "ctr_step_many: output missing");
     if (autoreset && !b.work) return fail(CTR_EINVAL, "ctr_step_many: autoreset needs batch->work");

@@ -7,6 +7,8 @@
 * configs[4] (65 536 envs, compliant, RK4 at 400 steps/m) at full size: joint constraints and
   step outputs hold for the whole batch, and a 4 096-env subset of the last step matches the
   oracle (tips <= 1e-11 m, joints / reward bit-exact).
+* configs[4]'s lane-pair step against the one-lane FK operator, and the same envs in a permuted
+  order (the work-ranked deal must not change any env's result).
 * bench.py's steady-state window (staggered episodes, refills inside the window), its plain line
   and --dump-outputs (repeatable from run to run), the --full legs, and its two-rank entry point
   (gloo rehearsal on one GPU).
@@ -203,3 +205,36 @@ def test_configs4_pair_step_matches_one_lane_fk(cuda, systems, rand):
     torch.cuda.synchronize()
     np.testing.assert_array_equal(env.nfev.cpu().numpy(), st["nfev"].cpu().numpy())
     assert np.abs(env.achieved_goal.cpu().numpy() - tip.cpu().numpy()).max() < 1e-12
+
+
+def test_configs4_pair_step_is_independent_of_env_placement(cuda):
+    """The pair step deals a workgroup's envs onto lane pairs by a counting sort whose order (LDS
+    atomics) is not fixed, so an env's result must not depend on where it lands.  The same envs in
+    a permuted order (moved inside and across two 512-lane workgroups, the second ragged) step to
+    the same bits: observation, reward, done, success, error, tip, joints, RHS count, status.
+    Domain randomisation off: its tables are keyed by the env number, which the permutation changes."""
+    import torch
+    from ctr_reach_amd import CtrReachVecEnv
+    n = 2 * 256 - 37
+    kw = dict(device=cuda, seed=4, integrator="rk4", rk4_steps_per_m=100, model="compliant",
+              select_systems=[0, 1, 2, 3], domain_rand=0.0, autoreset=False)
+    env_a, env_b = CtrReachVecEnv(n, **kw), CtrReachVecEnv(n, **kw)
+    env_a.reset()
+    env_b.reset()
+    rng = np.random.default_rng(8)
+    perm = rng.permutation(n)
+    home, src = np.arange(n) // 256, perm // 256
+    assert (home != src).any() and ((home == src) & (perm != np.arange(n))).any()
+    a = torch.tensor(_acts(rng, n, env_a.action_space.high), device=cuda)
+    p = torch.tensor(perm, device=cuda)
+    for k in ("joints", "system", "desired_goal"):
+        getattr(env_b, k).copy_(getattr(env_a, k)[p])
+    for env, act in ((env_a, a), (env_b, a[p].contiguous())):
+        env.enable_nfev()
+        env.step(act)
+    torch.cuda.synchronize()
+    assert len(set(env_a.system.cpu().numpy().tolist())) == 4 and int(env_a.nfev.min().item()) > 0
+    inv = torch.tensor(np.argsort(perm), device=cuda)
+    for k in ("obs", "reward", "done", "success", "error", "achieved_goal", "joints", "nfev", "status"):
+        want, got = getattr(env_a, k).cpu().numpy(), getattr(env_b, k)[inv].cpu().numpy()
+        assert want.tobytes() == got.tobytes(), k

@@ -1,7 +1,9 @@
 """Host-side logic and the C-ABI surface (no GPU needed)."""
 import ctypes
+import glob
 import os
 import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -255,3 +257,16 @@ def test_gather_row_pack_roundtrip():
     assert torch.equal(t2, tip.float())
     assert torch.equal(r2, reward) and not torch.signbit(r2[r2 == 0]).any()
     assert torch.equal(d2, done.bool()) and torch.equal(s2, success.bool())
+
+
+@pytest.mark.skipif(shutil.which("patch") is None, reason="no patch(1)")
+@pytest.mark.parametrize("name", sorted(os.path.basename(p) for p in
+                                        glob.glob(os.path.join(ROOT, "tools", "experiments", "*.patch"))))
+def test_experiment_patches_apply_to_the_sources(tmp_path, name):
+    """What is kept outside the product sources as a patch (tools/experiments/*.patch, applied by
+    build_rev.sh) still applies to them: every hunk, on a copy of csrc."""
+    rel = os.path.join("gym-ctr-reach_amd", "csrc")
+    shutil.copytree(os.path.join(ROOT, rel), tmp_path / rel)
+    with open(os.path.join(ROOT, "tools", "experiments", name), "rb") as f:
+        r = subprocess.run(["patch", "-p1", "--dry-run"], cwd=tmp_path, stdin=f, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
