@@ -2141,3 +2141,149 @@ int ctr_compute_reward(const double *achieved, const double *desired, int64_t n,
 
 #include "ctr_her.inc"
 #include "ctr_gather.inc"
+
+// ------------------------------------------------------------------------------------------
+// Damped-least-squares position IK (src/jacobian_controller.py:19-73) with the forward-difference
+// Jacobian of k_jacobian, the whole loop and a waypoint path in one launch.  One target on 7
+// lanes (lane c < 6: the FK at q + eps e_c, lane 6: at q), and the 7 lanes in ONE wave: 9 targets
+// on lanes 0..62, lane 63 idle, 36 targets per workgroup (k_jacobian's grid).  A wave owns its 9
+// targets from q0 to the last waypoint and exchanges the tips with wave shuffles, so the loop has
+// no workgroup barrier (targets of a workgroup stop after different iteration counts).  Every
+// lane of the wave stays in the loop and executes every shuffle until the wave's last target has
+// stopped; a stopped or idle lane only skips its FK.  After the exchange the 7 lanes of a target
+// hold the same J and e and take the same update, so the result does not depend on the target's
+// place in the batch.  (It is emitted last in the code object: k_step's place there stays.)
+namespace {
+
+constexpr int IK_WAVE_ENVS = 64 / 7;
+static_assert(IK_WAVE_ENVS * (BLOCK / 64) == JAC_ENVS, "k_ik: 9 targets per wave, k_jacobian's 36 per workgroup");
+
+template <int MODE>
+__global__ __launch_bounds__(BLOCK) void k_ik(KCfg kc, ctr_ik_t a)
+{
+    __shared__ SysK s_sys[CTR_MAX_SYSTEMS];
+    stage_systems(kc, s_sys);
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const bool seated = lane < 7 * IK_WAVE_ENVS;
+    const int grp = seated ? lane / 7 : 0, col = lane % 7;        // the idle lane reads group 0's lanes
+    const int64_t e = (int64_t)blockIdx.x * JAC_ENVS + wave * IK_WAVE_ENVS + grp;
+    const bool mine = seated && e < a.n;
+    const int s = mine && a.sys_idx ? clamp_sys(a.sys_idx[e], kc.c.n_systems) : 0;
+    double q[6];
+    #pragma unroll
+    for (int i = 0; i < 6; ++i) q[i] = mine ? a.q0[6 * e + i] : 0.0;
+    uint32_t status = 0;
+    for (int w = 0; w < a.waypoints; ++w) {
+        const int64_t row = e * a.waypoints + w;
+        double err = INFINITY;
+        int32_t iters = 0;
+        bool live = mine && a.num > 0;
+        // wave-uniform: the wave iterates until its last target has stopped (<= num times)
+        for (int it = 0; it < a.num && __ballot(live) != 0; ++it) {
+            double r[3] = {0.0, 0.0, 0.0};
+            if (live) {
+                double qp[6];
+                #pragma unroll
+                for (int i = 0; i < 6; ++i) qp[i] = i == col ? q[i] + a.eps : q[i];
+                FkStats st = {0, 0, 0, 0, 0};
+                fk_dispatch_d<MODE>(kc, s_sys[s], qp, r, st);
+                status |= st.status;
+            }
+            // all 64 lanes from here: the base tip from lane 6 of the group, then this lane's
+            // column (k_jacobian's arithmetic), then every column to every lane of the group
+            double p[3], jc[3], J[3][6];
+            #pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                p[k] = __shfl(r[k], 7 * grp + 6);
+                jc[k] = (r[k] - p[k]) / a.eps;
+            }
+            #pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                #pragma unroll
+                for (int c = 0; c < 6; ++c) J[k][c] = __shfl(jc[k], 7 * grp + c);
+            }
+            double d[3];
+            bool ok = true;
+            #pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                d[k] = (live ? a.targets[3 * row + k] : 0.0) - p[k];
+                ok = ok && isfinite(d[k]);
+                #pragma unroll
+                for (int c = 0; c < 6; ++c) ok = ok && isfinite(J[k][c]);
+            }
+            if (live && !ok) {
+                // a NaN FK (an iterate in a tube gap): stop at the last finite iterate
+                err = NAN;
+                live = false;
+            }
+            // x = (J J^T + lam I)^-1 d by Cholesky (symmetric positive definite, lam > 0)
+            double m00 = a.lam, m10 = 0.0, m11 = a.lam, m20 = 0.0, m21 = 0.0, m22 = a.lam;
+            #pragma unroll
+            for (int c = 0; c < 6; ++c) {
+                m00 += J[0][c] * J[0][c];
+                m10 += J[1][c] * J[0][c];
+                m11 += J[1][c] * J[1][c];
+                m20 += J[2][c] * J[0][c];
+                m21 += J[2][c] * J[1][c];
+                m22 += J[2][c] * J[2][c];
+            }
+            const double l00 = sqrt(m00), l10 = m10 / l00, l20 = m20 / l00;
+            const double l11 = sqrt(m11 - l10 * l10), l21 = (m21 - l20 * l10) / l11;
+            const double l22 = sqrt(m22 - l20 * l20 - l21 * l21);
+            const double y0 = d[0] / l00, y1 = (d[1] - l10 * y0) / l11, y2 = (d[2] - l20 * y0 - l21 * y1) / l22;
+            const double x2 = y2 / l22, x1 = (y1 - l21 * x2) / l11, x0 = (y0 - l10 * x1 - l20 * x2) / l00;
+            if (live) {
+                #pragma unroll
+                for (int c = 0; c < 6; ++c) q[c] += J[0][c] * x0 + J[1][c] * x1 + J[2][c] * x2;
+                err = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+                iters += 1;
+                live = err >= a.tol && iters < a.num;
+            }
+        }
+        if (mine) {
+            // the group's lanes share the row's stores: lane c < 6 its joint, lane 6 err and iters
+            #pragma unroll
+            for (int c = 0; c < 6; ++c)
+                if (c == col) a.q[6 * row + c] = q[c];
+            if (col == 6) {
+                a.err[row] = err;
+                a.iters[row] = iters;
+            }
+        }
+    }
+    if (mine && a.status && status) atomicOr(&a.status[e], status);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ctr_ik_dls(const ctr_env_config_t *cfg, const ctr_ik_t *ik, void *stream)
+{
+    if (int r = check_cfg(cfg)) return r;
+    if (!ik) return fail(CTR_EINVAL, "ctr_ik_dls: ik is NULL");
+    const ctr_ik_t a = *ik;
+    if (a.n < 0 || a.n > 0x7fffffff) return fail(CTR_EINVAL, "ctr_ik_dls: n out of range");
+    if (a.waypoints < 1) return fail(CTR_EINVAL, "ctr_ik_dls: waypoints must be >= 1");
+    if (a.num < 0) return fail(CTR_EINVAL, "ctr_ik_dls: num must be >= 0");
+    if ((int64_t)a.waypoints * a.num > CTR_IK_MAX_ITERS)
+        return fail(CTR_EINVAL, "ctr_ik_dls: waypoints * num must be <= CTR_IK_MAX_ITERS (8192)");
+    if (!(a.lam > 0.0) || !isfinite(a.lam)) return fail(CTR_EINVAL, "ctr_ik_dls: lam must be finite and > 0");
+    if (!(a.tol >= 0.0)) return fail(CTR_EINVAL, "ctr_ik_dls: tol must be >= 0");
+    if (!(a.eps != 0.0) || !isfinite(a.eps)) return fail(CTR_EINVAL, "ctr_ik_dls: eps must be finite and nonzero");
+    if (a.n == 0) return 0;
+    if (!a.targets) return fail(CTR_EINVAL, "ctr_ik_dls: targets is NULL");
+    if (!a.q0) return fail(CTR_EINVAL, "ctr_ik_dls: q0 is NULL");
+    if (!a.q) return fail(CTR_EINVAL, "ctr_ik_dls: q is NULL");
+    if (!a.err) return fail(CTR_EINVAL, "ctr_ik_dls: err is NULL");
+    if (!a.iters) return fail(CTR_EINVAL, "ctr_ik_dls: iters is NULL");
+    const uintptr_t q0b = (uintptr_t)a.q0, qb = (uintptr_t)a.q;
+    if (q0b < qb + (uintptr_t)a.n * a.waypoints * 6 * sizeof(double) && qb < q0b + (uintptr_t)a.n * 6 * sizeof(double))
+        return fail(CTR_EINVAL, "ctr_ik_dls: q0 must not overlap q");
+    const KCfg kc = make_kcfg(cfg);
+    const unsigned grid = (unsigned)((a.n + JAC_ENVS - 1) / JAC_ENVS);
+    CTR_LAUNCH(k_ik, kc.mode, dim3(grid), 0, (hipStream_t)stream, kc, a);
+    return hip_check("ctr_ik_dls launch");
+}
+
+}  // extern "C"

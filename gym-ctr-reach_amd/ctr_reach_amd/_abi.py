@@ -10,12 +10,13 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CTR_REACH_AMD_LIB") or os.path.join(HERE, "lib", "libctr_reach_amd.so")
 
-CTR_ABI_VERSION = 16
+CTR_ABI_VERSION = 17
 CTR_IPC_HANDLE_BYTES = 64
 CTR_GATHER_MAX_RANKS = 16
 CTR_MAX_SYSTEMS = 8
 CTR_POOL_MAX = 192          # ctr_batch_t.pool_depth limit
 CTR_STEP_MANY_MAX = 64      # steps of one ctr_step_many launch
+CTR_IK_MAX_ITERS = 8192     # waypoints * num of one ctr_ik_dls launch
 CTR_HER_SCAN_TILE = 1024
 CTR_INTEGRATOR_RK45_SCIPY = 0
 CTR_INTEGRATOR_RK4 = 1
@@ -141,6 +142,13 @@ class CtrActionSeq(ctypes.Structure):
     _fields_ = [("a", _P * CTR_STEP_MANY_MAX)]
 
 
+class CtrIk(ctypes.Structure):
+    """ctr_ik_t: one ctr_ik_dls launch (ABI 17)."""
+    _fields_ = [("n", ctypes.c_int64), ("waypoints", ctypes.c_int32), ("num", ctypes.c_int32),
+                ("lam", ctypes.c_double), ("tol", ctypes.c_double), ("eps", ctypes.c_double),
+                ("targets", _P), ("q0", _P), ("sys_idx", _P), ("q", _P), ("err", _P), ("iters", _P), ("status", _P)]
+
+
 class CtrGatherPush(ctypes.Structure):
     _fields_ = [("src", _P), ("n", ctypes.c_int64), ("world", ctypes.c_int32), ("pad", ctypes.c_int32),
                 ("dst", _P * CTR_GATHER_MAX_RANKS), ("seqw", _P * CTR_GATHER_MAX_RANKS), ("ticket", _P),
@@ -192,7 +200,8 @@ EXPORTED = ("ctr_abi_version", "ctr_last_error", "ctr_fk", "ctr_set_action", "ct
             "ctr_pool_refill", "ctr_compute_reward", "ctr_domain_params", "ctr_fk_tables", "ctr_jacobian", "ctr_fk_shape",
             "ctr_her_open", "ctr_her_record", "ctr_her_sample", "ctr_step_her", "ctr_pool_requeue",
             "ctr_ipc_get_handle", "ctr_ipc_open", "ctr_ipc_close", "ctr_seqw_alloc", "ctr_seqw_free", "ctr_copy_list",
-            "ctr_gather_wait", "ctr_gather_push", "ctr_gather_publish", "ctr_refill_carry_bytes", "ctr_step_many")
+            "ctr_gather_wait", "ctr_gather_push", "ctr_gather_publish", "ctr_refill_carry_bytes", "ctr_step_many",
+            "ctr_ik_dls")
 
 _lib = None
 
@@ -251,6 +260,8 @@ def load(path=None):
     if hasattr(L, "ctr_step_many"):                # ABI 16
         L.ctr_step_many.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch), ctypes.POINTER(CtrActionSeq),
                                     i32, ctypes.POINTER(CtrStepOut), i32, _P]
+    if hasattr(L, "ctr_ik_dls"):                   # ABI 17
+        L.ctr_ik_dls.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrIk), _P]
     if hasattr(L, "ctr_refill_carry_bytes"):       # ABI 12
         L.ctr_refill_carry_bytes.argtypes = [i64]
         L.ctr_refill_carry_bytes.restype = i64

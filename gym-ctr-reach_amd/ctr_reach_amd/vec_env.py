@@ -598,6 +598,43 @@ class CtrReachVecEnv(object):
         _abi.check(rc, "ctr_jacobian")
         return tip, jac
 
+    def ik_dls(self, targets, q0, system=None, lam=0.25, num=500, tol=1e-3, eps=1e-4, stream=None):
+        """Damped-least-squares position IK (dls_ik_position_only, src/jacobian_controller.py:19-73)
+        on this env's FK, the whole loop in ONE ctr_ik_dls launch.  targets [M, 3], or [M, K, 3]
+        for a path of K waypoints per target (waypoint k starts from waypoint k - 1's solution);
+        q0 [M, 6].  Returns device tensors (q, err, iters, status) shaped like the targets:
+        q [M, 6] / [M, K, 6] float64, err and iters [M] / [M, K] (float64, int32), status [M]
+        (uint32 as int32: the CTR_STATUS_* bits of every FK the target ran).  err is NaN where the
+        iterate left the nesting constraints (q is then the last finite iterate)."""
+        torch = _torch()
+        pd = torch.as_tensor(targets, dtype=torch.float64, device=self.device)
+        if pd.dim() not in (2, 3) or pd.shape[-1] != 3:
+            raise ValueError("targets must be [M, 3] or [M, K, 3]")
+        path = pd.dim() == 3
+        m, k = pd.shape[0], (pd.shape[1] if path else 1)
+        if k < 1:
+            raise ValueError("a path needs at least one waypoint")
+        num = int(num)
+        if k * num > _abi.CTR_IK_MAX_ITERS:
+            raise ValueError("waypoints * num = %d exceeds CTR_IK_MAX_ITERS = %d for one launch (dls_ik_path cuts a "
+                             "path into launches)" % (k * num, _abi.CTR_IK_MAX_ITERS))
+        pd = pd.contiguous()
+        q_in = torch.as_tensor(q0, dtype=torch.float64, device=self.device).reshape(-1, 6).contiguous()
+        if q_in.shape[0] != m:
+            raise ValueError("q0 must be [M, 6] for targets [M, ...]")
+        s = None if system is None else torch.as_tensor(system, dtype=torch.int32, device=self.device).reshape(-1).expand(m).contiguous()
+        q = torch.empty((m, k, 6), dtype=torch.float64, device=self.device)
+        err = torch.empty((m, k), dtype=torch.float64, device=self.device)
+        iters = torch.empty((m, k), dtype=torch.int32, device=self.device)
+        status = torch.zeros((m,), dtype=torch.int32, device=self.device)
+        ik = _abi.CtrIk(m, k, num, float(lam), float(tol), float(eps), _abi.ptr(pd), _abi.ptr(q_in), _abi.ptr(s),
+                        _abi.ptr(q), _abi.ptr(err), _abi.ptr(iters), _abi.ptr(status))
+        rc = self.lib.ctr_ik_dls(self.cfg, ik, _abi.stream_ptr(stream))
+        _abi.check(rc, "ctr_ik_dls")
+        if not path:
+            return q[:, 0], err[:, 0], iters[:, 0], status
+        return q, err, iters, status
+
     def domain_parameters(self, stream=None):
         """Each env's current tube table (Model.current_sys_parameters after randomize_parameters,
         model.py:20-28): dict of [n, 3] float64 device tensors L, L_c, EI, GJ, U_x, U_y,

@@ -27,6 +27,8 @@
  *   ctr_fk_tables       Model.forward_kinematics with per-row tube tables  envs/model.py:30-70
  *   ctr_fk_shape        Model.forward_kinematics + Model.r / r1 / r2 / r3  envs/model.py:30-70,119-174
  *   ctr_jacobian        CTR_Model.jac (finite differences)             envs/CTR_Python/CTR_Model.py:251-262
+ *   ctr_ik_dls          dls_ik_position_only(model, q0, P_d, lam, num, tol) src/jacobian_controller.py:19-73
+ *                       (and its use along the line / circle / helix waypoint paths of src/)
  *   ctr_domain_params   Model.current_sys_parameters after randomize_parameters
  *                                                                          envs/model.py:20-28, model_utils.py:5-35
  *   ctr_her_open / ctr_her_record / ctr_her_sample
@@ -46,7 +48,7 @@
 extern "C" {
 #endif
 
-#define CTR_ABI_VERSION 16
+#define CTR_ABI_VERSION 17
 #define CTR_MAX_SYSTEMS 8
 #define CTR_POOL_MAX 192          /* ctr_batch_t.pool_depth limit (reset slots per environment) */
 #define CTR_EINVAL (-1)
@@ -371,6 +373,39 @@ int ctr_fk_shape(const float *joints, const int32_t *sys_idx, const ctr_system_t
  * status bits are OR-ed in. */
 int ctr_jacobian(const double *joints, const int32_t *sys_idx, int64_t n, const ctr_env_config_t *cfg, double eps,
                  double *tip, double *jac, uint32_t *status, void *stream);
+
+/* Damped-least-squares position IK on that Jacobian (ABI 17), the loop of dls_ik_position_only
+ * (src/jacobian_controller.py:19-73) for n targets in ONE launch.  Per target and waypoint, at
+ * most num times:
+ *     p, J = FK(q), (FK(q + eps e_c) - FK(q)) / eps           (ctr_jacobian's arithmetic)
+ *     e    = p_d - p
+ *     e or J not finite: err = NaN, stop (q and iters unchanged: the last finite iterate)
+ *     q   += J^T (J J^T + lam I)^-1 e ;  err = |e| ;  iters += 1 ;  stop once |e| < tol
+ * (the stop is checked after the update, as the reference does).  With waypoints = K > 1 a target
+ * follows a path: waypoint k starts from the q waypoint k - 1 ended with (q0 for k = 0), also
+ * after a NaN stop; err starts at +inf and iters at 0 for every waypoint, so num = 0 returns
+ * q0, +inf, 0.  The 7 FKs of a target run on 7 lanes of one wave, which owns its 9 targets
+ * from q0 to the last waypoint: a target costs FKs only while its wave still has one running.
+ * A target's result does not depend on n or on its place in the batch.
+ * One launch runs at most waypoints * num <= CTR_IK_MAX_ITERS iterations per target; longer paths
+ * are cut at waypoint boundaries by the caller (the next call's q0 = the last waypoint's q).
+ * Every mode ctr_jacobian supports.  Nothing is allocated; stream-ordered; the struct is read at
+ * the call.  A refused argument is CTR_EINVAL before any HIP call; n = 0 is a no-op. */
+#define CTR_IK_MAX_ITERS 8192
+typedef struct ctr_ik_t {
+    int64_t n;                 /* targets                                                        */
+    int32_t waypoints;         /* K >= 1                                                         */
+    int32_t num;               /* iterations per waypoint, >= 0, K * num <= CTR_IK_MAX_ITERS     */
+    double  lam, tol, eps;     /* lam > 0 finite; tol >= 0 (not NaN); eps finite, != 0           */
+    const double  *targets;    /* [n][K][3]  device                                              */
+    const double  *q0;         /* [n][6]     device, must not overlap q                          */
+    const int32_t *sys_idx;    /* [n] or NULL (system 0)                                         */
+    double   *q;               /* [n][K][6]  q at the end of each waypoint                       */
+    double   *err;             /* [n][K]                                                         */
+    int32_t  *iters;           /* [n][K]                                                         */
+    uint32_t *status;          /* [n] or NULL: CTR_STATUS_* of every FK run, OR-ed in            */
+} ctr_ik_t;
+int ctr_ik_dls(const ctr_env_config_t *cfg, const ctr_ik_t *ik, void *stream);
 
 /* n_substeps x Obs.set_action, in place on joints [n][6] (device). */
 int ctr_set_action(const ctr_env_config_t *cfg, float *joints, const int32_t *sys_idx,
