@@ -9,6 +9,9 @@
 //                 rigid model + fixed-step RK4: one env per 8-lane group (fk_group_rigid4)
 //   k_step_many   the k steps of a refill period in one launch: the staging once, then k_step's
 //                 per-step code k times per wave, no inter-wave wait between the steps
+//   k_step_tail   k_step_many, and each wave then does the period's refill work (suspended resets by
+//                 claim, its own envs' new resets) instead of a k_refill launch; k_tail_close
+//                 follows it and as a rule exits at once (ctr_step_period, at the end of the file)
 //   k_reset       CtrReachEnv.reset, TWO lanes per env (goal FK | start FK in parallel),
 //                 for the queued / masked envs                        (envs/ctr_reach_env.py:70-114)
 //   k_refill      precomputes queued resets into the pool, two lanes per reset
@@ -844,7 +847,8 @@ __device__ __forceinline__ void step_finish_group(const KCfg &kc, const ctr_batc
 // queue) and the fused push of the step's rows.
 __device__ __forceinline__ void step_epilogue(const ctr_batch_t &b, const ctr_step_out_t &o, int32_t autoreset,
                                               const StepFlags &fl, int64_t e, bool live, const ctr_gather_push_t *gp,
-                                              bool slot_free0, float4 grow, bool zero_miss = true)
+                                              bool slot_free0, float4 grow, bool zero_miss = true,
+                                              bool queue = true)
 {
     if (autoreset) {
         if (autoreset == CTR_AUTORESET_POOLED) {
@@ -855,7 +859,8 @@ __device__ __forceinline__ void step_epilogue(const ctr_batch_t &b, const ctr_st
             const int32_t one[1] = {(int32_t)e};
             wave_append(miss_counter(b), miss_items(b), b.n, fl.miss, one, 1);
         }
-        if (b.pool_depth > 0) {
+        // (queue = false, k_step_tail: the wave keeps its own refill entries, step_body_tail)
+        if (queue && b.pool_depth > 0) {
             const int32_t two[2] = {(int32_t)e, (int32_t)(fl.pooled_r + (uint32_t)b.pool_depth)};
             wave_append(b.refill, b.refill + 1, b.refill_cap, fl.pooled, two, 2);
         }
@@ -918,7 +923,8 @@ __device__ __forceinline__ float (*next_action_lds())[BLOCK]
 // env's next step -- the state step_finish left, carried instead of read back, and the row of
 // next_actions (NULL after the last step), whose load is issued before the FK and parked in LDS
 // across it (not in registers the FK loop would have to keep, like the finish's inputs).
-template <int MODE, bool HER, bool MANY>
+// QUEUE = false (k_step_tail): a pooled reset is not appended to the refill queue.
+template <int MODE, bool HER, bool MANY, bool QUEUE = true>
 __device__ __forceinline__ void step_one(const KCfg &kc, const ctr_batch_t &b, const float *__restrict__ actions,
                                          const ctr_step_out_t &o, int32_t autoreset, const ctr_her_t *her,
                                          const SysK *s_sys, const ctr_tube_raw_t *s_raw, int64_t e, int j, bool in,
@@ -1020,7 +1026,7 @@ __device__ __forceinline__ void step_one(const KCfg &kc, const ctr_batch_t &b, c
             for (int i = 0; i < 6; ++i) { r.q[i] = q[i]; r.a[i] = next_action_lds()[i][threadIdx.x]; }
         }
     }
-    step_epilogue(b, o, autoreset, fl, e, live, gp, slot_free0, grow, !MANY);
+    step_epilogue(b, o, autoreset, fl, e, live, gp, slot_free0, grow, !MANY, QUEUE);
 }
 
 // k_step / k_step_her: the staging, then one step.
@@ -1469,9 +1475,61 @@ constexpr int CARRY_SUBS = 64;
 struct CarryHdr {
     int32_t count[2][CARRY_SUBS];   // resets on each sub-list of each list
     int32_t parity;                 // the list the next refill reads
-    int32_t pad[127];
+    // k_step_tail (the period's refill in the step kernel's tail); all zero between launches
+    int32_t claim;                  // next reset of the list read to hand out
+    int32_t fresh;                  // resets the period's waves have taken from the pool so far
+    int32_t unsure;                 // resets suspended on an epoch that may have been stale
+    int32_t ticket;                 // workgroups that have finished
+    int32_t fix;                    // for k_tail_close: TAIL_FIX_*
+    int32_t pad[122];
 };
 static_assert(sizeof(CarryHdr) == 1024, "CarryHdr layout");
+static_assert(offsetof(CarryHdr, parity) == 512, "CarryHdr: the counts first (ctr_refill_carry_bytes)");
+
+// What k_step_tail's last workgroup leaves for k_tail_close: nothing (it has flipped the lists),
+// or the resets it suspended that ctr_pool_refill would have finished -- all of them (the period's
+// resets do not all fit on the list: no budget), or those fewer than refill_lead ahead of an
+// environment whose epoch the suspending wave may have read before the environment's last reset.
+constexpr int TAIL_FIX_NONE = 0, TAIL_FIX_ALL = 1, TAIL_FIX_NEAR = 2;
+
+// An atomic add whose old value is waited for: when it has come back the add is performed, so a
+// ticket taken afterwards orders after it.  k_step_tail's last workgroup reads, in the same
+// kernel, counters other workgroups added to; an add without a used return value is not waited
+// for by the barrier before the ticket and could land after the read (or after the reset).
+__device__ __forceinline__ int32_t atomic_add_performed(int32_t *p, int32_t v)
+{
+    const int32_t old = atomicAdd(p, v);
+    asm volatile("" : : "v"(old));               // a use: the compiler waits for the return here
+    return old;
+}
+
+// The lists as one refill pass sees them: it resumes list `in` and appends to the other.
+struct CarryLists {
+    CarryHdr *ch;
+    const CarryRec *in_list;
+    CarryRec *out_list;
+    int out;                        // the list appended to
+    int nsub;
+    int64_t sub_cap;
+};
+
+// The sub-lists ctr_pool_refill's grid uses for batch b (k_refill: one per workgroup up to
+// CARRY_SUBS), which every kernel that reads or appends to the lists must agree on.
+__host__ __device__ inline int refill_grid(int64_t n, int64_t lanes_per_reset)
+{
+    const int64_t g = (lanes_per_reset * n + BLOCK - 1) / BLOCK;
+    return (int)(g < 256 ? g : 256);
+}
+
+// The budget rule of a refill of `queued` new and `carried` resumed resets (k_refill): a budget
+// only while every sub-list can take all the pairs its workgroups may suspend.
+__host__ __device__ inline bool refill_budget_fits(int64_t queued, int64_t carried, int64_t G, int nsub, int64_t sub_cap)
+{
+    const int64_t per_pass = G * (BLOCK / 64) * 32;
+    const int64_t passes = (queued + carried + per_pass - 1) / per_pass;
+    const int64_t inflow = (G + nsub - 1) / nsub * (BLOCK / 64) * 32 * passes;
+    return inflow <= sub_cap;
+}
 
 // One FK of a refill: the scipy-RK45 FK (either model) runs at most `budget` iterations (the
 // compliant RK4 FK at most `budget` RK4 steps) and can start from a suspended state (fk_lane /
@@ -1501,14 +1559,172 @@ __device__ __forceinline__ bool fk_refill(const KCfg &kc, const SysK &sy, const 
     }
 }
 
+// A suspended pair's record: each lane its own FK (the state, or the tip of a finished one), the
+// odd lane the pair's fields.
+__device__ __forceinline__ void carry_write(CarryRec *ro, bool odd, bool fin, bool ofin, const double tip[3],
+                                            uint32_t fst, const FkSuspend &sv, const float oq[6], const float qv[6],
+                                            int64_t e, uint32_t r, int s, uint32_t stat)
+{
+    if (fin) {
+        #pragma unroll
+        for (int k = 0; k < 3; ++k) ro->tip[odd][k] = tip[k];
+        ro->fstat[odd] = fst;
+    } else {
+        ro->fk[odd] = sv;
+    }
+    if (odd) {
+        #pragma unroll
+        for (int k = 0; k < 6; ++k) { ro->qd[k] = oq[k]; ro->q0[k] = qv[k]; }
+        ro->e = (int32_t)e;
+        ro->r = r;
+        ro->sys = s;
+        ro->stat = stat;
+        ro->done = (ofin ? 1u : 0u) | (fin ? 2u : 0u);
+    }
+}
+
+// One reset of a resumable refill on its lane pair (every lane of the wave calls it; carried,
+// queued, rin, e, r, ep are pair-uniform): a reset resumed from the list read (carried: its record
+// rin) or a new one (queued), for reset number r of env e whose epoch is ep.
+// far_budget: the iterations a reset at least refill_lead ahead runs here (-1: to the end).
+// SPILL (k_step_tail, k_tail_close; not k_refill, whose budget rule keeps every sub-list within
+// its capacity): a pair whose sub-list is full goes to the next one, and one that finds them all
+// full goes back onto the refill queue.  unsure_below: a carried pair suspended fewer than this many resets ahead is
+// counted in CarryHdr::unsure (k_step_tail: ep may be older than the period's last reset).
+template <int MODE, bool SPILL>
+__device__ __forceinline__ void refill_pair(const KCfg &kc, const ctr_batch_t &b, const SysK *s_sys,
+                                            const ctr_tube_raw_t *s_raw, const CarryLists &L, bool carried, bool queued,
+                                            const CarryRec *rin, int64_t e, uint32_t r, uint32_t ep, int far_budget,
+                                            uint32_t unsure_below = 0u)
+{
+    const int lane = threadIdx.x & 63;
+    const bool odd = ResetLanes<MODE>::odd();
+    const int64_t ps = (carried || queued) ? (int64_t)(r % (uint32_t)b.pool_depth) * b.n + e : 0;
+    // only the resets the env can still take from its ring, epoch + 1 .. epoch + P.  With a
+    // ring shallower than the refill interval one period can queue both r + P (the env took
+    // reset r from the ring) and r + 2P (the miss sweep took r + P when the ring ran dry):
+    // the two map to one slot, and writing both would race (fields of two resets mixed)
+    const uint32_t lead = (queued || carried) ? r - ep - 1u : 0u;   // resets before r
+    // (queued or carried alike: a suspended reset the env has passed meanwhile -- a miss sweep
+    // took it -- or whose slot already holds it is dropped, not finished into a stale slot)
+    const bool fresh = (queued || carried) && b.pool[ps].r != r && lead < (uint32_t)b.pool_depth;
+    const uint64_t genv = (uint64_t)(b.env_base + e);
+    // every queued entry draws (draws are a pure function of (seed, env, r); one that is not
+    // fresh discards its joints), so the pool_r / epoch loads behind `fresh` overlap the
+    // sampling instead of preceding it
+    const int s = queued ? sample_system(kc.c.seed, r, genv, kc.c.n_systems) : (carried ? rin->sys : 0);
+    float qv[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    uint32_t stat = 0;
+    // the wave's new resets draw together (sample_joints_wave): every lane calls it
+    if (sample_joints_wave(s_sys[s], kc.c.seed, r, odd ? 1u : 0u, genv, queued, qv) > 1000)
+        stat |= CTR_STATUS_SAMPLER_STUCK;
+    stat |= __shfl_xor(stat, 1);                      // the pair's sampling status
+    bool had = false;                                 // this lane's FK finished in an earlier refill
+    if (carried) {
+        #pragma unroll
+        for (int k = 0; k < 6; ++k) qv[k] = odd ? rin->q0[k] : rin->qd[k];
+        stat = rin->stat;
+        had = ((rin->done >> (odd ? 1 : 0)) & 1u) != 0;
+    }
+    double tip[3] = {0.0, 0.0, 0.0};
+    uint32_t fst = 0;                                 // this lane's FK status
+    bool fin = true;
+    FkSuspend sv;
+    if (had) {
+        #pragma unroll
+        for (int k = 0; k < 3; ++k) tip[k] = rin->tip[odd][k];
+        fst = rin->fstat[odd];
+    }
+    // a reset at least refill_lead resets ahead of its env runs on the budget (again, if it
+    // was suspended before); a nearer one finishes here, before the env can need it
+    const int budget = (far_budget >= 0 && lead >= (uint32_t)b.refill_lead) ? far_budget : 0x7fffffff;
+    if (!had && fresh) {
+        FkStats st = {0, 0, 0, 0, 0};
+        fin = fk_refill<MODE>(kc, episode_sys(kc, s_sys, s_raw, s, r, genv), qv, tip, st,
+                              carried ? &rin->fk[odd] : nullptr, &sv, budget);
+        fst = st.status;
+    }
+    const bool active = fresh;
+    const bool ofin = __shfl_xor((int)fin, 1) != 0;
+    double otip[3];
+    float oq[6];
+    #pragma unroll
+    for (int k = 0; k < 3; ++k) otip[k] = __shfl_xor(tip[k], 1);
+    #pragma unroll
+    for (int k = 0; k < 6; ++k) oq[k] = __shfl_xor(qv[k], 1);
+    const uint32_t ofst = __shfl_xor(fst, 1);
+    if (active && fin && ofin && odd)                 // both FKs done: the pool slot
+        pool_store(b.pool + ps, oq, qv, otip, tip, s, stat | fst | ofst, r);
+    // a pair with a suspended FK goes onto the other list (one atomic per wave)
+    bool keep = active && !(fin && ofin);
+    if constexpr (!SPILL) {
+        const uint64_t m = __ballot(keep && odd);
+        if (m) {
+            const int leader = __builtin_ctzll(m);
+            int slot = 0;
+            const int sub = blockIdx.x % L.nsub;
+            if (lane == leader) slot = atomicAdd(&L.ch->count[L.out][sub], __popcll(m));
+            slot = __shfl(slot, leader) + __popcll(m & ((1ull << (lane | 1)) - 1ull));
+            if (keep && slot < L.sub_cap)
+                carry_write(L.out_list + sub * L.sub_cap + slot, odd, fin, ofin, tip, fst, sv, oq, qv, e, r, s, stat);
+        }
+    } else {
+        if (unsure_below) {
+            const uint64_t u = __ballot(keep && odd && carried && lead < unsure_below);
+            if (u && lane == __builtin_ctzll(u)) atomic_add_performed(&L.ch->unsure, __popcll(u));
+        }
+        for (int at = 0; at < L.nsub; ++at) {
+            const uint64_t m = __ballot(keep && odd);
+            if (!m) break;
+            const int leader = __builtin_ctzll(m);
+            const int cnt = __popcll(m);
+            int base = 0;
+            const int sub = (int)((blockIdx.x + (unsigned)at) % (unsigned)L.nsub);
+            if (lane == leader) {
+                base = atomicAdd(&L.ch->count[L.out][sub], cnt);
+                // the part past the sub-list's end is given back (the count never falls below
+                // the capacity again, so no slot is handed out twice)
+                const int64_t room = L.sub_cap - base;
+                const int over = room >= cnt ? 0 : (room <= 0 ? cnt : cnt - (int)room);
+                if (over) atomic_add_performed(&L.ch->count[L.out][sub], -over);
+            }
+            const int slot = __shfl(base, leader) + __popcll(m & ((1ull << (lane | 1)) - 1ull));
+            if (keep && slot < L.sub_cap) {
+                carry_write(L.out_list + sub * L.sub_cap + slot, odd, fin, ofin, tip, fst, sv, oq, qv, e, r, s, stat);
+                keep = false;
+            }
+        }
+        // every sub-list is full: more resets than the lists hold, so the budget rule fails and
+        // TAIL_FIX_ALL follows (refill_budget_fits); the pair goes back onto the queue, and
+        // k_tail_close computes it from its draws.  (k_tail_close appends with SPILL too, but never
+        // gets here: it only moves records that fitted on one list onto the other, emptied one of
+        // the same capacity -- under TAIL_FIX_NEAR it does not read the queue, and adds nothing to it)
+        const int32_t two[2] = {(int32_t)e, (int32_t)r};
+        wave_append(b.refill, b.refill + 1, b.refill_cap, keep && odd, two, 2);
+    }
+}
+
 // Pool refill: the resets suspended by the previous refill (finished here), then the entries
 // (env, reset number) queued in b.refill; two lanes per reset, as reset_pair: the even lane draws
 // the desired joints and runs the goal FK, the odd lane draws the start joints and runs the start
 // FK (ctr_reach_env.py:100-112).
-template <int MODE>
-__global__ __launch_bounds__(BLOCK) void k_refill(KCfg kc, ctr_batch_t b)
+// CLOSE (k_tail_close, after a k_step_tail whose last workgroup left TAIL_FIX_ALL / TAIL_FIX_NEAR):
+// no queue; the list read is the one k_step_tail appended to, the survivors go back onto the
+// other (emptied) one and the lists are not flipped, so the next refill reads them there.  A reset
+// fewer than refill_lead ahead finishes (TAIL_FIX_ALL: every reset); the others are copied as
+// they are (a budget of no iterations: the period has run theirs).
+template <int MODE, bool CLOSE>
+__device__ __forceinline__ void refill_body(const KCfg &kc, const ctr_batch_t &b)
 {
     constexpr bool RESUMABLE = refill_resumable<MODE>();  // all but the rigid model's RK4
+    static_assert(!CLOSE || RESUMABLE, "k_tail_close: the resumable refill only");
+    int fix = TAIL_FIX_NONE;
+    if constexpr (CLOSE) {
+        // almost always nothing to do: leave before staging the tables (block-uniform)
+        if (b.carry == nullptr) return;
+        fix = static_cast<const CarryHdr *>(b.carry)->fix;
+        if (fix == TAIL_FIX_NONE) return;
+    }
     __shared__ SysK s_sys[CTR_MAX_SYSTEMS];
     __shared__ ctr_tube_raw_t s_raw[CTR_MAX_SYSTEMS];
     __shared__ int64_t s_count, s_carried;
@@ -1532,11 +1748,12 @@ __global__ __launch_bounds__(BLOCK) void k_refill(KCfg kc, ctr_batch_t b)
     int par_l = 0;
     int32_t cnt_a = 0, cnt_b = 0;
     if (threadIdx.x < 64 && carry_on) {
-        par_l = ch->parity & 1;
+        par_l = (ch->parity & 1) ^ (CLOSE ? 1 : 0);
         cnt_a = ch->count[0][threadIdx.x];
         cnt_b = ch->count[1][threadIdx.x];
     }
-    if (threadIdx.x == 0) s_count = min((int64_t)b.refill[0], b.refill_cap);
+    // (CLOSE: the queue holds what found every sub-list full, which comes with TAIL_FIX_ALL)
+    if (threadIdx.x == 0) s_count = (CLOSE && fix != TAIL_FIX_ALL) ? 0 : min((int64_t)b.refill[0], b.refill_cap);
     // (the rigid model's FK never reads the segment LUT: no staging of it)
     stage_systems<(MODE & 4) == 0>(kc, s_sys, s_raw, &stg);
     if (threadIdx.x < 64) {                               // wave 0: prefix sums of the counts read
@@ -1554,11 +1771,13 @@ __global__ __launch_bounds__(BLOCK) void k_refill(KCfg kc, ctr_batch_t b)
         if (threadIdx.x == CARRY_SUBS - 1) {
             s_carried = incl;
             // a budget only while every sub-list can take all the pairs its workgroups may suspend
+            // (refill_budget_fits); -1: none
             const int64_t G = min((int64_t)gridDim.x, (int64_t)256);
-            const int64_t per_pass = G * (BLOCK / 64) * 32;
-            const int64_t passes = (s_count + incl + per_pass - 1) / per_pass;
-            const int64_t inflow = (G + nsub - 1) / nsub * (BLOCK / 64) * 32 * passes;
-            s_budget = (carry_on && b.refill_budget > 0 && inflow <= sub_cap) ? b.refill_budget : 0;
+            if constexpr (CLOSE)
+                s_budget = fix == TAIL_FIX_NEAR ? 0 : -1;
+            else
+                s_budget = (carry_on && b.refill_budget > 0 && refill_budget_fits(s_count, incl, G, nsub, sub_cap))
+                               ? b.refill_budget : -1;
         }
     }
     __syncthreads();
@@ -1578,7 +1797,6 @@ __global__ __launch_bounds__(BLOCK) void k_refill(KCfg kc, ctr_batch_t b)
     const int64_t my_pair = (threadIdx.x & 63) / RL::U;
     const int64_t total = s_count + c;
     const int64_t count = blockIdx.x < G ? total : 0;
-    const int lane = threadIdx.x & 63;
     const bool odd = RL::odd();
     for (int64_t base = 0; base < count; base += per_pass) {
         const int64_t i = base + my_pair * waves + my_wave;
@@ -1617,92 +1835,9 @@ __global__ __launch_bounds__(BLOCK) void k_refill(KCfg kc, ctr_batch_t b)
             e = b.refill[1 + 2 * (i - c)];
             r = (uint32_t)b.refill[2 + 2 * (i - c)];
         }
-        const int64_t ps = (carried || queued) ? (int64_t)(r % (uint32_t)b.pool_depth) * b.n + e : 0;
-        // only the resets the env can still take from its ring, epoch + 1 .. epoch + P.  With a
-        // ring shallower than the refill interval one period can queue both r + P (the env took
-        // reset r from the ring) and r + 2P (the miss sweep took r + P when the ring ran dry):
-        // the two map to one slot, and writing both would race (fields of two resets mixed)
-        const uint32_t lead = (queued || carried) ? r - (uint32_t)b.epoch[e] - 1u : 0u;   // resets before r
-        // (queued or carried alike: a suspended reset the env has passed meanwhile -- a miss sweep
-        // took it -- or whose slot already holds it is dropped, not finished into a stale slot)
-        const bool fresh = (queued || carried) && b.pool[ps].r != r && lead < (uint32_t)b.pool_depth;
-        const uint64_t genv = (uint64_t)(b.env_base + e);
-        // every queued entry draws (draws are a pure function of (seed, env, r); one that is not
-        // fresh discards its joints), so the pool_r / epoch loads behind `fresh` overlap the
-        // sampling instead of preceding it
-        const int s = queued ? sample_system(kc.c.seed, r, genv, kc.c.n_systems) : (carried ? rin->sys : 0);
-        float qv[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        uint32_t stat = 0;
-        // the wave's new resets draw together (sample_joints_wave): every lane calls it
-        if (sample_joints_wave(s_sys[s], kc.c.seed, r, odd ? 1u : 0u, genv, queued, qv) > 1000)
-            stat |= CTR_STATUS_SAMPLER_STUCK;
-        stat |= __shfl_xor(stat, 1);                      // the pair's sampling status
-        bool had = false;                                 // this lane's FK finished in an earlier refill
-        if (carried) {
-            #pragma unroll
-            for (int k = 0; k < 6; ++k) qv[k] = odd ? rin->q0[k] : rin->qd[k];
-            stat = rin->stat;
-            had = ((rin->done >> (odd ? 1 : 0)) & 1u) != 0;
-        }
-        double tip[3] = {0.0, 0.0, 0.0};
-        uint32_t fst = 0;                                 // this lane's FK status
-        bool fin = true;
-        FkSuspend sv;
-        if (had) {
-            #pragma unroll
-            for (int k = 0; k < 3; ++k) tip[k] = rin->tip[odd][k];
-            fst = rin->fstat[odd];
-        } else if (fresh) {
-            // a reset at least refill_lead resets ahead of its env runs on the budget (again, if it
-            // was suspended before); a nearer one finishes here, before the env can need it
-            const int budget = (s_budget > 0 && lead >= (uint32_t)b.refill_lead) ? s_budget : 0x7fffffff;
-            FkStats st = {0, 0, 0, 0, 0};
-            fin = fk_refill<MODE>(kc, episode_sys(kc, s_sys, s_raw, s, r, genv), qv, tip, st,
-                                  carried ? &rin->fk[odd] : nullptr, &sv, budget);
-            fst = st.status;
-        }
-        const bool active = fresh;
-        const bool ofin = __shfl_xor((int)fin, 1) != 0;
-        double otip[3];
-        float oq[6];
-        #pragma unroll
-        for (int k = 0; k < 3; ++k) otip[k] = __shfl_xor(tip[k], 1);
-        #pragma unroll
-        for (int k = 0; k < 6; ++k) oq[k] = __shfl_xor(qv[k], 1);
-        const uint32_t ofst = __shfl_xor(fst, 1);
-        if (active && fin && ofin && odd)                 // both FKs done: the pool slot
-            pool_store(b.pool + ps, oq, qv, otip, tip, s, stat | fst | ofst, r);
-        if constexpr (RESUMABLE) {
-            // a pair with a suspended FK goes onto the other list (one atomic per wave)
-            const bool keep = active && !(fin && ofin);
-            const uint64_t m = __ballot(keep && odd);
-            if (m) {
-                const int leader = __builtin_ctzll(m);
-                int slot = 0;
-                const int sub = blockIdx.x % nsub;
-                if (lane == leader) slot = atomicAdd(&ch->count[par ^ 1][sub], __popcll(m));
-                slot = __shfl(slot, leader) + __popcll(m & ((1ull << (lane | 1)) - 1ull));
-                if (keep && slot < sub_cap) {
-                    CarryRec *ro = out_list + sub * sub_cap + slot;
-                    if (fin) {
-                        #pragma unroll
-                        for (int k = 0; k < 3; ++k) ro->tip[odd][k] = tip[k];
-                        ro->fstat[odd] = fst;
-                    } else {
-                        ro->fk[odd] = sv;
-                    }
-                    if (odd) {
-                        #pragma unroll
-                        for (int k = 0; k < 6; ++k) { ro->qd[k] = oq[k]; ro->q0[k] = qv[k]; }
-                        ro->e = (int32_t)e;
-                        ro->r = r;
-                        ro->sys = s;
-                        ro->stat = stat;
-                        ro->done = (ofin ? 1u : 0u) | (fin ? 2u : 0u);
-                    }
-                }
-            }
-        }
+        const uint32_t ep = (queued || carried) ? (uint32_t)b.epoch[e] : 0u;
+        const CarryLists lists = {ch, in_list, out_list, par ^ 1, nsub, sub_cap};
+        refill_pair<MODE, CLOSE>(kc, b, s_sys, s_raw, lists, carried, queued, rin, e, r, ep, s_budget);
     }
     // the last workgroup to finish clears the queue and the list it read, and flips the lists
     // (every workgroup read the counts at its start): a ticket at refill[1 + 2 cap] instead of a
@@ -1711,14 +1846,21 @@ __global__ __launch_bounds__(BLOCK) void k_refill(KCfg kc, ctr_batch_t b)
     if (threadIdx.x == 0) {
         int32_t *ticket = b.refill + 1 + 2 * b.refill_cap;
         if (atomicAdd(ticket, 1) == (int32_t)gridDim.x - 1) {
-            b.refill[0] = 0;
+            if (!CLOSE || fix == TAIL_FIX_ALL) b.refill[0] = 0;
             if (carry_on) {
                 for (int k = 0; k < CARRY_SUBS; ++k) ch->count[par][k] = 0;
-                ch->parity = par ^ 1;
+                if constexpr (CLOSE) ch->fix = TAIL_FIX_NONE;     // (the lists stay as they are)
+                else ch->parity = par ^ 1;
             }
             *ticket = 0;
         }
     }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(BLOCK) void k_refill(KCfg kc, ctr_batch_t b)
+{
+    refill_body<MODE, false>(kc, b);
 }
 
 // Requeue: every env's resets epoch + 1 .. epoch + P that its pool slots do not hold (after a seed
@@ -2021,8 +2163,11 @@ int ctr_step(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const float 
     return step_launch(cfg, batch, actions, out, autoreset, nullptr, stream);
 }
 
-int ctr_step_many(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_action_seq_t *actions, int32_t k,
-                  const ctr_step_out_t *out, int32_t autoreset, void *stream)
+// ctr_step_many's checks, all before any HIP call (ctr_step_period repeats them); on success
+// *kc_out, *seq_out hold the kernel arguments.
+static int step_many_check(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_action_seq_t *actions,
+                           int32_t k, const ctr_step_out_t *out, int32_t autoreset, KCfg *kc_out,
+                           ctr_action_seq_t *seq_out)
 {
     if (int r = check_cfg(cfg)) return r;
     if (!batch || !out || !actions) return fail(CTR_EINVAL, "ctr_step_many: NULL argument");
@@ -2048,8 +2193,20 @@ int ctr_step_many(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const c
     if (autoreset == CTR_AUTORESET_POOLED && b.pool_depth <= 0)
         return fail(CTR_EINVAL, "ctr_step_many: CTR_AUTORESET_POOLED needs a reset pool");
     if (b.pool_depth > 0 && !cfg->resample_joints) return fail(CTR_EINVAL, "the reset pool needs resample_joints");
+    *kc_out = kc;
+    for (int32_t i = 0; i < CTR_STEP_MANY_MAX; ++i) seq_out->a[i] = i < k ? actions->a[i] : nullptr;
+    return 0;
+}
+
+int ctr_step_many(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_action_seq_t *actions, int32_t k,
+                  const ctr_step_out_t *out, int32_t autoreset, void *stream)
+{
+    KCfg kc;
     ctr_action_seq_t seq;                        // by value into the kernel arguments
-    for (int32_t i = 0; i < CTR_STEP_MANY_MAX; ++i) seq.a[i] = i < k ? actions->a[i] : nullptr;
+    if (int r = step_many_check(cfg, batch, actions, k, out, autoreset, &kc, &seq)) return r;
+    const ctr_batch_t b = *batch;
+    const ctr_step_out_t o = *out;
+    if (b.n == 0) return 0;
     const dim3 g(grid_for(b.n)), blk(BLOCK);
     const size_t shm = lane_lds_bytes(kc);
     hipStream_t s = (hipStream_t)stream;
@@ -2284,6 +2441,248 @@ int ctr_ik_dls(const ctr_env_config_t *cfg, const ctr_ik_t *ik, void *stream)
     const unsigned grid = (unsigned)((a.n + JAC_ENVS - 1) / JAC_ENVS);
     CTR_LAUNCH(k_ik, kc.mode, dim3(grid), 0, (hipStream_t)stream, kc, a);
     return hip_check("ctr_ik_dls launch");
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// ctr_step_period: the k steps of a refill period and the period's refill in one kernel.  A wave
+// that has taken its 64 envs through the steps (k_step_many's loop, without the queue appends)
+// goes straight on to the refill's work, with no device-wide join and no wait of any kind:
+//   1. the resets the previous refill suspended (the list read, complete at launch) are handed out
+//      in chunks of 32 lane pairs by one atomic on CarryHdr::claim, so the early waves take most of
+//      them;
+//   2. then the wave's own new entries.  An env that took resets ep0 + 1 .. ep1 from the pool in
+//      the period has queued (e, ep0 + 1 + P) .. (e, ep1 + P): two epochs per lane say it all.
+// Both with k_refill's code for one reset (refill_pair).  What k_refill decides from the state
+// after the period's last step cannot all be known here: whether the budget applies at all (its
+// rule counts the period's entries), and the epoch of another wave's env, which may still be
+// stepping (an older epoch makes a reset look further ahead than it is).  Both can only turn a
+// reset that k_refill would finish into a suspended one, so the waves suspend on what they see, the
+// last workgroup to finish checks (every count is final then) and almost always just flips the
+// lists; else it leaves CarryHdr::fix for k_tail_close, which follows every launch and finishes
+// those resets (as a rule it exits at once).
+// (Emitted after every other kernel: their places in the code object stay.)
+namespace {
+
+template <int MODE>
+constexpr bool tail_mode() { return !pair_mode<MODE>() && refill_resumable<MODE>() && MODE != 1; }
+// (MODE 1, the compliant model's RK45 with y pre-curvature: its step loop and the refill's FK
+// together fill 256 + 256 registers and spill 64 B per lane to scratch; the step kernels use no scratch, so ctr_step_period refuses the mode and it keeps
+// ctr_step_many followed by k_refill)
+
+template <int MODE>
+__device__ __forceinline__ void step_body_tail(const KCfg &kc, const ctr_batch_t &b, const ctr_action_seq_t &seq,
+                                               int32_t k, const ctr_step_out_t &o, int32_t autoreset)
+{
+    __shared__ SysK s_sys[CTR_MAX_SYSTEMS];
+    __shared__ ctr_tube_raw_t s_raw[CTR_MAX_SYSTEMS];
+    __shared__ int32_t s_pref[CARRY_SUBS + 1];           // sub-list starts of the list read
+    __shared__ int32_t s_carried;
+    __shared__ int s_par, s_last;
+    __shared__ uint32_t s_ep0[BLOCK];                    // each env's epoch before the period
+    __shared__ int32_t s_own[BLOCK / 64][64 + 1];        // per wave: starts of its lanes' new entries
+    const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool live = e < b.n;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    StageRegs stg;
+    stage_load(kc, stg);
+    __builtin_amdgcn_sched_barrier(0);       // keep the table loads ahead of the row loads
+    StepRows r;
+    step_rows_load(b, seq.a[0], live ? e : b.n - 1, r);
+    // the lists as ctr_pool_refill's grid lays them out (k_refill)
+    CarryHdr *ch = static_cast<CarryHdr *>(b.carry);
+    const int G = refill_grid(b.n, 2);
+    const int nsub = G < CARRY_SUBS ? G : CARRY_SUBS;
+    const bool carry_on = ch != nullptr && b.carry_cap >= nsub;
+    const int64_t sub_cap = b.carry_cap / nsub;
+    int par_l = 0;
+    int32_t cnt_a = 0, cnt_b = 0;
+    if (threadIdx.x < 64 && carry_on) {
+        par_l = ch->parity & 1;
+        cnt_a = ch->count[0][threadIdx.x];
+        cnt_b = ch->count[1][threadIdx.x];
+    }
+    stage_systems<true>(kc, s_sys, s_raw, &stg);
+    if (autoreset == CTR_AUTORESET_POOLED && blockIdx.x == 0 && threadIdx.x == 0) {   // as k_step_many
+        b.work[(b.work_parity & 1) ^ 1] = 0;
+        if (k > 1) b.work[b.work_parity & 1] = 0;
+    }
+    if (threadIdx.x < 64) {                               // wave 0: prefix sums of the counts read
+        int32_t incl = (int32_t)min((int64_t)(par_l ? cnt_b : cnt_a), sub_cap);
+        #pragma unroll
+        for (int off = 1; off < CARRY_SUBS; off <<= 1) {
+            const int32_t v = __shfl_up(incl, off);
+            if ((int)threadIdx.x >= off) incl += v;
+        }
+        s_pref[threadIdx.x + 1] = incl;
+        if (threadIdx.x == 0) {
+            s_pref[0] = 0;
+            s_par = par_l;
+        }
+        if (threadIdx.x == CARRY_SUBS - 1) s_carried = incl;
+    }
+    s_ep0[threadIdx.x] = r.ep;
+    __syncthreads();
+    #pragma unroll 1
+    for (int32_t i = 0; i < k; ++i) {
+        const float *nxt = i + 1 < k ? seq.a[i + 1] : nullptr;
+        step_one<MODE, false, true, false>(kc, b, nullptr, o, autoreset, nullptr, s_sys, s_raw, e, 0, live, live, r,
+                                           nullptr, true, nxt);
+    }
+    // ---- the refill.  Nothing below waits for another wave.
+    const int par = s_par;
+    const int32_t c = carry_on ? s_carried : 0;
+    CarryRec *recs = carry_on ? reinterpret_cast<CarryRec *>(reinterpret_cast<char *>(ch) + sizeof(CarryHdr)) : nullptr;
+    const CarryLists lists = {ch, recs ? recs + par * b.carry_cap : nullptr,
+                              recs ? recs + (par ^ 1) * b.carry_cap : nullptr, par ^ 1, nsub, sub_cap};
+    // the budget as far as it can be known here (the last workgroup checks k_refill's rule)
+    const int far_budget = (carry_on && b.refill_budget > 0) ? b.refill_budget : -1;
+    // this wave's new entries: lane l's env took own_n resets from the pool
+    const uint32_t ep0 = s_ep0[threadIdx.x];
+    const int32_t own_n = (live && b.pool_depth > 0) ? (int32_t)(r.ep - ep0) : 0;
+    int32_t own_incl = own_n;
+    #pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int32_t v = __shfl_up(own_incl, off);
+        if (lane >= off) own_incl += v;
+    }
+    const int32_t own_total = __shfl(own_incl, 63);
+    s_own[wave][lane + 1] = own_incl;
+    if (lane == 0) s_own[wave][0] = 0;
+    if (carry_on && own_total > 0 && lane == 0) atomic_add_performed(&ch->fresh, own_total);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // s_own: read by the wave's other lanes
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int pair = lane >> 1;
+    // one loop for both (one copy of the refill's code): 1. suspended resets, by claim; 2. the
+    // wave's own new entries
+    bool claiming = c > 0;
+    int32_t own_base = 0;
+    for (;;) {
+        bool carried = false, queued = false;
+        const CarryRec *rin = nullptr;
+        int64_t pe = 0;
+        uint32_t pr = 0, pep = 0;
+        if (claiming) {
+            int32_t base = 0;
+            if (lane == 0) base = atomicAdd(&ch->claim, 32);
+            base = __shfl(base, 0);
+            claiming = base < c;
+            const int32_t i = base + pair;
+            carried = i < c;
+            if (carried) {                                // sub-list j: s_pref[j] <= i < s_pref[j + 1]
+                int lo = 0;
+                #pragma unroll
+                for (int step = CARRY_SUBS / 2; step >= 1; step >>= 1)
+                    if (s_pref[lo + step] <= i) lo += step;
+                rin = lists.in_list + lo * sub_cap + (i - s_pref[lo]);
+                pe = rin->e;
+                pr = rin->r;
+                pep = (uint32_t)b.epoch[pe];              // (another wave's env: at least its epoch at launch)
+            }
+        }
+        if (!claiming) {                                  // (wave-uniform; a claim past the list's end lands here)
+            if (own_base >= own_total) break;
+            const int32_t i = own_base + pair;
+            own_base += 32;
+            queued = i < own_total;
+            int lo = 0;
+            if (queued) {                                 // lane lo: s_own[lo] <= i < s_own[lo + 1]
+                #pragma unroll
+                for (int step = 32; step >= 1; step >>= 1)
+                    if (s_own[wave][lo + step] <= i) lo += step;
+            }
+            const uint32_t q0 = s_ep0[wave * 64 + lo];
+            pe = queued ? (int64_t)blockIdx.x * BLOCK + wave * 64 + lo : 0;
+            pr = queued ? q0 + 1u + (uint32_t)(i - s_own[wave][lo]) + (uint32_t)b.pool_depth : 0u;
+            pep = queued ? q0 + (uint32_t)(s_own[wave][lo + 1] - s_own[wave][lo]) : 0u;   // the env's epoch now
+        }
+        // an env takes at most one reset per step: another wave's epoch read now is at most k behind
+        refill_pair<MODE, true>(kc, b, s_sys, s_raw, lists, carried, queued, rin, pe, pr, pep, far_budget,
+                                carried ? (uint32_t)b.refill_lead + (uint32_t)k : 0u);
+    }
+    if (!carry_on) return;                                // no lists: every reset has finished
+    // the last workgroup to finish: the list read is consumed, every count is final
+    __syncthreads();
+    if (threadIdx.x == 0) s_last = atomicAdd(&ch->ticket, 1) == (int32_t)gridDim.x - 1;
+    __syncthreads();
+    if (!s_last || threadIdx.x >= 64) return;
+    const int32_t fresh = __hip_atomic_load(&ch->fresh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int32_t unsure = __hip_atomic_load(&ch->unsure, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int32_t mine = __hip_atomic_load(&ch->count[par ^ 1][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool suspended = __ballot(mine > 0) != 0;
+    int fix = TAIL_FIX_NONE;
+    if (suspended) {
+        if (!refill_budget_fits(fresh, c, G, nsub, sub_cap)) fix = TAIL_FIX_ALL;
+        else if (unsure > 0) fix = TAIL_FIX_NEAR;
+    }
+    ch->count[par][lane] = 0;
+    if (lane == 0) {
+        ch->claim = 0;
+        ch->fresh = 0;
+        ch->unsure = 0;
+        ch->ticket = 0;
+        ch->fix = fix;
+        if (fix == TAIL_FIX_NONE) ch->parity = par ^ 1;
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(BLOCK) void k_step_tail(KCfg kc, ctr_batch_t b, ctr_action_seq_t seq, int32_t k,
+                                                     ctr_step_out_t o, int32_t autoreset)
+{
+    if constexpr (tail_mode<MODE>()) step_body_tail<MODE>(kc, b, seq, k, o, autoreset);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(BLOCK) void k_tail_close(KCfg kc, ctr_batch_t b)
+{
+    if constexpr (tail_mode<MODE>()) refill_body<MODE, true>(kc, b);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ctr_step_period(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_action_seq_t *actions, int32_t k,
+                    const ctr_step_out_t *out, void *stream)
+{
+    KCfg kc;
+    ctr_action_seq_t seq;                        // by value into the kernel arguments
+    if (int r = step_many_check(cfg, batch, actions, k, out, CTR_AUTORESET_POOLED, &kc, &seq)) return r;
+    // (the lane-pair and 8-lane group steps are refused above; their refills are not the two-lane
+    // resumable one either)
+    const ctr_batch_t b = *batch;
+    const ctr_step_out_t o = *out;
+    if (b.n == 0) return 0;
+    if (kc.mode == 1)
+        return fail(CTR_EINVAL, "ctr_step_period: not for the compliant model's scipy RK45 with y pre-curvature (the "
+                                "kernel would spill to scratch); use ctr_step_many and ctr_pool_refill");
+    const dim3 g(grid_for(b.n)), blk(BLOCK);
+    const size_t shm = lane_lds_bytes(kc);
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t ar = CTR_AUTORESET_POOLED;
+    switch (kc.mode) {
+    case 0: hipLaunchKernelGGL(k_step_tail<0>, g, blk, shm, s, kc, b, seq, k, o, ar); break;
+    case 2: hipLaunchKernelGGL(k_step_tail<2>, g, blk, shm, s, kc, b, seq, k, o, ar); break;   // (a build without the lane pairs)
+    case 3: hipLaunchKernelGGL(k_step_tail<3>, g, blk, shm, s, kc, b, seq, k, o, ar); break;
+    case 4: hipLaunchKernelGGL(k_step_tail<4>, g, blk, shm, s, kc, b, seq, k, o, ar); break;
+    default: hipLaunchKernelGGL(k_step_tail<5>, g, blk, shm, s, kc, b, seq, k, o, ar); break;
+    }
+    if (int r = hip_check("ctr_step_period launch")) return r;
+    // without the lists every reset has finished in the kernel: nothing to close
+    const int G = refill_grid(b.n, 2);
+    if (b.carry == nullptr || b.carry_cap < (G < CARRY_SUBS ? G : CARRY_SUBS)) return 0;
+    const dim3 gc((unsigned)G);
+    switch (kc.mode) {
+    case 0: hipLaunchKernelGGL(k_tail_close<0>, gc, blk, shm, s, kc, b); break;
+    case 2: hipLaunchKernelGGL(k_tail_close<2>, gc, blk, shm, s, kc, b); break;
+    case 3: hipLaunchKernelGGL(k_tail_close<3>, gc, blk, shm, s, kc, b); break;
+    case 4: hipLaunchKernelGGL(k_tail_close<4>, gc, blk, shm, s, kc, b); break;
+    default: hipLaunchKernelGGL(k_tail_close<5>, gc, blk, shm, s, kc, b); break;
+    }
+    return hip_check("ctr_step_period close launch");
 }
 
 }  // extern "C"

@@ -201,7 +201,7 @@ EXPORTED = ("ctr_abi_version", "ctr_last_error", "ctr_fk", "ctr_set_action", "ct
             "ctr_her_open", "ctr_her_record", "ctr_her_sample", "ctr_step_her", "ctr_pool_requeue",
             "ctr_ipc_get_handle", "ctr_ipc_open", "ctr_ipc_close", "ctr_seqw_alloc", "ctr_seqw_free", "ctr_copy_list",
             "ctr_gather_wait", "ctr_gather_push", "ctr_gather_publish", "ctr_refill_carry_bytes", "ctr_step_many",
-            "ctr_ik_dls")
+            "ctr_ik_dls", "ctr_step_period")
 
 _lib = None
 
@@ -260,6 +260,9 @@ def load(path=None):
     if hasattr(L, "ctr_step_many"):                # ABI 16
         L.ctr_step_many.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch), ctypes.POINTER(CtrActionSeq),
                                     i32, ctypes.POINTER(CtrStepOut), i32, _P]
+    if hasattr(L, "ctr_step_period"):              # added within ABI 17 (an older build lacks it)
+        L.ctr_step_period.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch),
+                                      ctypes.POINTER(CtrActionSeq), i32, ctypes.POINTER(CtrStepOut), _P]
     if hasattr(L, "ctr_ik_dls"):                   # ABI 17
         L.ctr_ik_dls.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrIk), _P]
     if hasattr(L, "ctr_refill_carry_bytes"):       # ABI 12

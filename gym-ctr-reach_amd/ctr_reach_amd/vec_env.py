@@ -99,7 +99,7 @@ class CtrReachVecEnv(object):
     def __init__(self, num_envs, device="cuda", seed=0, env_base=0, autoreset=True, record_info=True,
                  pool_depth=None, refill_interval=64, integrator="rk45_scipy", rk4_steps_per_m=100,
                  model="compliant", pack_outputs=False, obs_dtype="float32", refill_budget=None, fused_period=True,
-                 **kwargs):
+                 tail_refill=False, **kwargs):
         torch = _torch()
         kw = default_kwargs()
         kw.update(kwargs)
@@ -179,7 +179,15 @@ class CtrReachVecEnv(object):
         # capture_steps runs each refill period as one ctr_step_many launch where step_many can
         # (fused_period=False or CTR_FUSED_PERIOD=0: one launch per step, for A/B runs)
         self.fused_period = bool(fused_period) and os.environ.get("CTR_FUSED_PERIOD", "1") != "0"
-        self.fused_launches = 0   # ctr_step_many launches so far
+        self.fused_launches = 0   # ctr_step_many / ctr_step_period launches so far
+        # tail_refill: step_many runs a whole refill period as one ctr_step_period launch, the
+        # period's refill in the step kernel's tail instead of a ctr_pool_refill launch.  Off by
+        # default: the same bits, but measured no faster.  CTR_TAIL_REFILL=1 / 0
+        # turns it on / off whatever the keyword says (A/B runs of programs that do not pass it)
+        sw = os.environ.get("CTR_TAIL_REFILL", "")
+        self.tail_refill = ((sw == "1" or (bool(tail_refill) and sw != "0"))
+                            and hasattr(self.lib, "ctr_step_period"))
+        self.tail_launches = 0    # ctr_step_period launches so far (each also counts in refills)
         # reset pool: resets are a pure function of (seed, env id, reset number), so they are
         # precomputed in batches every `refill_interval` steps and consumed by a copy
         # depth >= the refill interval: every env then finds its next reset in the pool on every
@@ -448,6 +456,13 @@ class CtrReachVecEnv(object):
             return "auto-reset needs the reset pool, full (every reset of the steps precomputed)"
         return None
 
+    def _tail_eligible(self):
+        # ctr_step_period refuses the compliant model's scipy RK45 with y pre-curvature (its kernel
+        # would spill to scratch): that mode keeps ctr_step_many and the refill launch
+        if self.integrator == "rk45_scipy" and self.model == "compliant":
+            return not any(self.cfg.systems[s].Uy[i] != 0.0 for s in range(self.n_systems) for i in range(3))
+        return True
+
     def step_many(self, actions, stream=None):
         """len(actions) consecutive step_raw calls, each refill period's steps as one launch
         (ctr_step_many: a wave takes its envs through the period's steps without the device-wide
@@ -457,7 +472,10 @@ class CtrReachVecEnv(object):
         CTR_STEP_MANY_MAX steps.  actions: [N, 6] float32 contiguous device tensors, which must
         stay alive until the launches have run.  Raises RuntimeError where the steps need more
         than this launch gives (step_many_ineligible): HER, packed outputs or the push gather, the
-        lane-pair and 8-lane group modes, auto-reset without a full pool."""
+        lane-pair and 8-lane group modes, auto-reset without a full pool.
+        A chunk that is a whole refill period (it starts right after a refill and ends where the
+        next one falls due) runs with ``tail_refill`` as one ctr_step_period launch, its refill in
+        the step kernel's tail and no ctr_pool_refill launch; the results are the same bits."""
         torch = _torch()
         why = self.step_many_ineligible()
         if why:
@@ -483,12 +501,22 @@ class CtrReachVecEnv(object):
             seq = _abi.CtrActionSeq()
             for j in range(k):
                 seq.a[j] = actions[i + j].data_ptr()
-            rc = self.lib.ctr_step_many(self.cfg, self._batch, seq, k, self._out, mode, sp)
-            _abi.check(rc, "ctr_step_many")
+            # a whole period (from a refill to the next one): its refill in the same launch
+            tail = (self.tail_refill and mode == _abi.AUTORESET_POOLED and self._steps_since_refill == 0
+                    and k == self.refill_interval and self._tail_eligible())
+            if tail:
+                rc = self.lib.ctr_step_period(self.cfg, self._batch, seq, k, self._out, sp)
+                _abi.check(rc, "ctr_step_period")
+                self.tail_launches += 1
+            else:
+                rc = self.lib.ctr_step_many(self.cfg, self._batch, seq, k, self._out, mode, sp)
+                _abi.check(rc, "ctr_step_many")
             self.fused_launches += 1
             if self.autoreset and k % 2:
                 self._batch.work_parity ^= 1
-            if self.pool_depth:
+            if tail:
+                self.refills += 1              # the period's refill has run (no ctr_pool_refill launch)
+            elif self.pool_depth:
                 self._steps_since_refill += k
                 if self._steps_since_refill >= self.refill_interval:
                     self.refill_pool(stream)
@@ -499,7 +527,8 @@ class CtrReachVecEnv(object):
         into one HIP graph; ``StepGraph.replay()`` then runs them with a single launch, so a
         launch-bound batch (configs[1]: 4 096 envs, ~10 us kernels) is not paced by the host.
         Where step_many can run the env (and fused_period is on), each refill period is captured as
-        one ctr_step_many launch and its refill instead of refill_interval launches.  That capture
+        one ctr_step_many launch and its refill (with tail_refill: one ctr_step_period launch, the
+        refill in its tail) instead of refill_interval launches.  That capture
         checks the action tensors as step_many does (contiguous float32 [N, 6] on the env's device,
         else ValueError); the step-by-step capture takes their pointers unchecked, like step_raw.
 
@@ -803,7 +832,7 @@ class StepGraph(object):
         self.actions = [a for a in actions]
         self.stream = stream if stream is not None else torch.cuda.Stream(device=env.device)
         self.stream.wait_stream(torch.cuda.current_stream(env.device))
-        refills, sweeps, seq, fused = env.refills, env.sweeps, env.packed_seq, env.fused_launches
+        refills, sweeps, seq, fused, tails = env.refills, env.sweeps, env.packed_seq, env.fused_launches, env.tail_launches
         # each refill period as one launch (step_many) where the env allows it
         self.fused = env.fused_period and env.step_many_ineligible() is None
         self.graph = torch.cuda.CUDAGraph()
@@ -815,8 +844,10 @@ class StepGraph(object):
                     env.step_raw(a, self.stream)
         self.refills_per_replay = env.refills - refills
         self.fused_per_replay = env.fused_launches - fused
+        self.tails_per_replay = env.tail_launches - tails
         # the capture launched nothing: its host bookkeeping is undone, replay() redoes it
         env.refills, env.sweeps, env.packed_seq, env.fused_launches = refills, sweeps, seq, fused
+        env.tail_launches = tails
         assert env._steps_since_refill == 0 or not env.pool_depth
 
     def replay(self):
@@ -824,5 +855,6 @@ class StepGraph(object):
         self.graph.replay()
         self.env.refills += self.refills_per_replay
         self.env.fused_launches += self.fused_per_replay
+        self.env.tail_launches += self.tails_per_replay
         if self.env.packed_bufs is not None:
             self.env.packed_seq += self.steps

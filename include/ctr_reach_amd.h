@@ -441,6 +441,32 @@ typedef struct ctr_action_seq_t {
 int ctr_step_many(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_action_seq_t *actions,
                   int32_t k, const ctr_step_out_t *out, int32_t autoreset, void *stream);
 
+/* A whole refill period in one call (an entry point added within ABI 17: no existing entry point
+ * or struct changes, so the number stays; a caller that needs it looks the symbol up): ctr_step_many(..., CTR_AUTORESET_POOLED, ...) followed
+ * by ctr_pool_refill, with the refill's work done in the tail of the step kernel.  A wave that
+ * has taken its 64 environments through the k steps does not append their consumed resets to
+ * batch->refill; it goes straight on to the refill: it claims resets the previous refill suspended
+ * (chunks of the carry list, one atomic per chunk) until none are left, then computes the new
+ * resets of its own environments, with ctr_pool_refill's arithmetic and the same refill_budget /
+ * refill_lead rule, suspending onto the same carry list.  No wave waits for another.  The last
+ * workgroup to finish flips the carry lists; a second, small kernel follows, which as a rule exits
+ * at once: it finishes the resets ctr_pool_refill would not have suspended where the waves could
+ * not know that (the budget rule counts the whole period's resets; a wave may read another wave's
+ * epoch before that environment's last reset of the period).
+ * Afterwards the batch, the outputs, the pool and the set of suspended resets are what
+ * ctr_step_many and ctr_pool_refill leave (the carry lists' order aside), batch->refill is empty,
+ * and a ctr_pool_refill that follows finds nothing to do.  It interoperates with ctr_step,
+ * ctr_pool_refill, ctr_pool_requeue and checkpoints of the batch like ctr_pool_refill.
+ * The caller's promises: batch->refill is empty at the call (the call starts a period: the last
+ * launch on the batch was a refill), and CTR_AUTORESET_POOLED's promise holds for all k steps.
+ * Refused (CTR_EINVAL, before any HIP call) wherever ctr_step_many is -- which includes the two
+ * modes whose refill is not the two-lane resumable one, the rigid model's fixed-step RK4 (8-lane
+ * groups) and the compliant model's without y pre-curvature (lane pairs) -- without a reset pool,
+ * and for the compliant model's scipy RK45 with a y pre-curvature (that kernel would not fit the
+ * register file without scratch; use ctr_step_many and ctr_pool_refill).  Stream-ordered; nothing is allocated. */
+int ctr_step_period(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_action_seq_t *actions,
+                    int32_t k, const ctr_step_out_t *out, void *stream);
+
 /* CtrReachEnv.reset for the environments with mask[i] != 0 (mask NULL = all).
  * goal [n][3] or NULL (sample a goal), system [n] or NULL (sample uniformly).
  * Writes the reset observation to obs [n][obs_dim]. */
@@ -454,7 +480,8 @@ int ctr_pool_refill(const ctr_env_config_t *cfg, const ctr_batch_t *batch, void 
 
 /* Bytes of batch->carry for carry_cap resets per list (a header, then two lists of suspended
  * resets, each in 64 sub-lists); int32 counts[2][64] at byte 0 of the header give the resets each
- * sub-list holds (diagnostics). */
+ * sub-list holds (diagnostics).  The header's other words (the list parity, ctr_step_period's
+ * claim and completion words) are zero between launches except the parity. */
 int64_t ctr_refill_carry_bytes(int64_t carry_cap);
 
 /* Queue every environment's next pool_depth resets (epoch + 1 .. epoch + P) that its pool slots
