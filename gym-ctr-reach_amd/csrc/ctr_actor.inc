@@ -1,0 +1,312 @@
+// ctr_actor.inc -- the deterministic MLP actor (ctr_actor, and the actor of k_rollout): its
+// arithmetic, the packed weight blob and the host-side packer.  Included by ctr_kernels.hip inside
+// its anonymous namespace.
+//
+// The network (include/ctr_reach_amd.h, "MLP actor"): 1..3 hidden layers of width 32..256 (multiples
+// of 32) on the flat row x[in_dim] = [observation, achieved_goal, desired_goal], zero-padded to 32:
+//     x_hi = bf16(x);  x_lo = bf16(x - float(x_hi))
+//     h1   = bf16(relu(W1 x_hi + W1 x_lo + b1))        bf16 weights, f32 accumulation, f32 bias
+//     hl   = bf16(relu(Wl h(l-1) + bl))
+//     y    = Wout hL + bout ;  a_i = scale_i * tanhf(y_i)
+// relu(z) = z > 0 ? z : 0 (a NaN becomes 0); every bf16 rounding is to nearest even.
+//
+// Mapping: v_mfma_f32_32x32x16_bf16 with the weights as the A operand and the activations as the B
+// operand, whose 32 columns are 32 envs: a wave's 64 envs are two column tiles.  A layer's f32
+// result tile has its env on the lane and 16 of its features in the lane's registers, and the next
+// layer sums over features, so the tile, converted to bf16, IS the next layer's B fragment: no lane
+// movement and no LDS between the layers.  Register 8s + j of lane half h is feature
+// 16s + 8(j>>2) + 4h + (j&3) of the tile, so k-step s of the next layer runs over the tile's features
+// in that order, and the packer stores the weight fragments of every layer but the first in the same
+// order (actor_k_of: the only place that knows the permutation).  Lanes move twice: the input rows
+// (lane l owns env l; the first layer's fragment wants k = 8h + j of env 32c + (l & 31)) and the six
+// outputs (rows 0..3 on lane half 0, 4..5 on half 1), both by wave-local lane permutes.  Nothing in
+// the actor waits for another wave; an output column depends on its own input column only.
+//
+// Blob: per layer, per 32-row tile T, per k-step S, the 64 lanes' 8-element bf16 fragments (16 B
+// each, lane-major: one 1-KB ds_read_b128 sweep per MFMA); then the f32 biases of every layer, each
+// padded to whole 32-row tiles.
+
+typedef __bf16 actor_bf16x8 __attribute__((ext_vector_type(8)));
+typedef float actor_f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int ACTOR_LAYERS = CTR_ACTOR_MAX_HIDDEN + 1;         // the hidden layers and the output layer
+constexpr int ACTOR_TILES = CTR_ACTOR_MAX_WIDTH / 32;          // 32-row tiles of the widest layer
+
+// Kernel-argument copy of the actor, with the blob's layout.
+struct ActorK {
+    int32_t in_dim, n_hidden;
+    int32_t tiles[ACTOR_LAYERS];       // 32-row tiles of layer l's output (0 past the output layer)
+    uint32_t w_off[ACTOR_LAYERS];      // byte offset of layer l's fragments
+    uint32_t b_off[ACTOR_LAYERS];      // byte offset of layer l's biases
+    uint32_t bytes;                    // whole blob
+    float scale[6];
+    const void *blob;
+};
+
+// k index of element j of lane half h in k-step S of layer l (see the header comment).
+inline int actor_k_of(int l, int S, int h, int j)
+{
+    if (l == 0) return 16 * S + 8 * h + j;
+    return 32 * (S >> 1) + 16 * (S & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+}
+
+inline uint16_t actor_bf16_bits(float f)
+{
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);     // NaN stays NaN
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);                      // nearest even
+}
+
+// The shape checks of every actor entry point; fills the layout.
+int actor_layout(const ctr_actor_t *a, ActorK *ak)
+{
+    if (!a) return fail(CTR_EINVAL, "actor is NULL");
+    if (a->in_dim != 19 && a->in_dim != 20) return fail(CTR_EINVAL, "actor: in_dim must be obs_dim + 6 = 19 or 20");
+    if (a->n_hidden < 1 || a->n_hidden > CTR_ACTOR_MAX_HIDDEN)
+        return fail(CTR_EINVAL, "actor: n_hidden must be in 1..CTR_ACTOR_MAX_HIDDEN (3)");
+    for (int l = 0; l < a->n_hidden; ++l)
+        if (a->width[l] < 32 || a->width[l] > CTR_ACTOR_MAX_WIDTH || a->width[l] % 32)
+            return fail(CTR_EINVAL, "actor: every hidden width must be a multiple of 32 in 32..CTR_ACTOR_MAX_WIDTH (256)");
+    memset(ak, 0, sizeof *ak);
+    ak->in_dim = a->in_dim;
+    ak->n_hidden = a->n_hidden;
+    int64_t off = 0, wbytes = 0;
+    for (int l = 0; l <= a->n_hidden; ++l) {
+        const int tiles = l < a->n_hidden ? a->width[l] / 32 : 1;
+        const int ksteps = l == 0 ? 2 : a->width[l - 1] / 16;
+        ak->tiles[l] = tiles;
+        ak->w_off[l] = (uint32_t)off;
+        off += (int64_t)tiles * ksteps * 1024;
+    }
+    wbytes = off;
+    for (int l = 0; l <= a->n_hidden; ++l) {
+        ak->b_off[l] = (uint32_t)off;
+        off += (int64_t)ak->tiles[l] * 32 * 4;
+    }
+    if (off > CTR_ACTOR_MAX_BYTES) {
+        snprintf(g_err, sizeof g_err, "actor: the packed network (%lld B of weights + %lld B of biases) exceeds "
+                 "CTR_ACTOR_MAX_BYTES = %d B of LDS", (long long)wbytes, (long long)(off - wbytes), CTR_ACTOR_MAX_BYTES);
+        return CTR_EINVAL;
+    }
+    ak->bytes = (uint32_t)off;
+    return 0;
+}
+
+// ... and the checks of the entry points that run it.
+int actor_check(const ctr_actor_t *a, ActorK *ak)
+{
+    if (int r = actor_layout(a, ak)) return r;
+    for (int i = 0; i < 6; ++i) {
+        if (!isfinite(a->scale[i])) return fail(CTR_EINVAL, "actor: scale must be finite");
+        ak->scale[i] = a->scale[i];
+    }
+    if (!a->blob) return fail(CTR_EINVAL, "actor: blob is NULL");
+    if (((uintptr_t)a->blob & 15u) != 0) return fail(CTR_EINVAL, "actor: blob must be 16-B aligned");
+    ak->blob = a->blob;
+    return 0;
+}
+
+int actor_pack(const ctr_actor_t *a, const float *const *W, const float *const *b, void *blob_host)
+{
+    ActorK ak;
+    if (int r = actor_layout(a, &ak)) return r;
+    if (!W || !b || !blob_host) return fail(CTR_EINVAL, "ctr_actor_pack: NULL argument");
+    for (int l = 0; l <= a->n_hidden; ++l)
+        if (!W[l] || !b[l]) return fail(CTR_EINVAL, "ctr_actor_pack: NULL layer among W[0..n_hidden], b[0..n_hidden]");
+    char *out = static_cast<char *>(blob_host);
+    memset(out, 0, ak.bytes);
+    for (int l = 0; l <= a->n_hidden; ++l) {
+        const int rows = l < a->n_hidden ? a->width[l] : 6;
+        const int cols = l == 0 ? a->in_dim : a->width[l - 1];
+        const int ksteps = l == 0 ? 2 : cols / 16;
+        for (int T = 0; T < ak.tiles[l]; ++T)
+            for (int S = 0; S < ksteps; ++S)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int j = 0; j < 8; ++j) {
+                        const int row = 32 * T + (lane & 31), k = actor_k_of(l, S, lane >> 5, j);
+                        const uint16_t v = (row < rows && k < cols) ? actor_bf16_bits(W[l][(size_t)row * cols + k]) : 0;
+                        memcpy(out + ak.w_off[l] + ((size_t)(T * ksteps + S) * 64 + lane) * 16 + 2 * j, &v, 2);
+                    }
+        memcpy(out + ak.b_off[l], b[l], (size_t)rows * 4);
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Device side.  The blob sits in dynamic LDS behind the per-lane domain tables (lane_bytes of
+// them), at the next 16-B boundary (the static LDS in front of the dynamic region need not be a
+// multiple of 16; a misaligned ds_read_b128 is replayed): launch with ACTOR_LDS_SLACK more.
+constexpr size_t ACTOR_LDS_SLACK = 16;
+
+__device__ __forceinline__ char *actor_lds_base(size_t lane_bytes)
+{
+    char *p = reinterpret_cast<char *>(s_lane_dyn) + lane_bytes;
+    const uint32_t a = (uint32_t)(size_t)(__attribute__((address_space(3))) char *)p;
+    return p + ((0u - a) & 15u);
+}
+
+// Every lane of the workgroup: the blob from global memory into LDS (a barrier must follow).
+__device__ __forceinline__ void actor_stage(const ActorK &ak, char *lds)
+{
+    const uint4 *src = static_cast<const uint4 *>(ak.blob);
+    uint4 *dst = reinterpret_cast<uint4 *>(lds);
+    for (uint32_t i = threadIdx.x; i < ak.bytes / 16; i += BLOCK) dst[i] = src[i];
+}
+
+__device__ __forceinline__ actor_bf16x8 actor_frag(const char *w, int index, int lane)
+{
+    return *reinterpret_cast<const actor_bf16x8 *>(w + (size_t)index * 1024 + lane * 16);
+}
+
+// The flat row of an env from its observation (already rounded to f32), achieved and desired goal.
+__device__ __forceinline__ void actor_row(const float ob[14], const float ag[3], const float dg[3], bool multi,
+                                          float x[20])
+{
+    #pragma unroll
+    for (int k = 0; k < 13; ++k) x[k] = ob[k];
+    x[13] = multi ? ob[13] : ag[0];
+    x[14] = multi ? ag[0] : ag[1];
+    x[15] = multi ? ag[1] : ag[2];
+    x[16] = multi ? ag[2] : dg[0];
+    x[17] = multi ? dg[0] : dg[1];
+    x[18] = multi ? dg[1] : dg[2];
+    x[19] = multi ? dg[2] : 0.f;
+}
+
+// bias, relu, bf16: the f32 tile T of a layer becomes k-steps 2T, 2T + 1 of the next one
+__device__ __forceinline__ void actor_activate(const actor_f32x16 &acc, const float *bias, int T, int h,
+                                               actor_bf16x8 &f0, actor_bf16x8 &f1)
+{
+    float z[16];
+    #pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const float4 bb = *reinterpret_cast<const float4 *>(bias + 32 * T + 8 * g + 4 * h);
+        z[4 * g] = acc[4 * g] + bb.x;
+        z[4 * g + 1] = acc[4 * g + 1] + bb.y;
+        z[4 * g + 2] = acc[4 * g + 2] + bb.z;
+        z[4 * g + 3] = acc[4 * g + 3] + bb.w;
+    }
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        f0[j] = (__bf16)(z[j] > 0.f ? z[j] : 0.f);
+        f1[j] = (__bf16)(z[8 + j] > 0.f ? z[8 + j] : 0.f);
+    }
+}
+
+// The whole network for the wave's 64 envs, one 32-env column tile after the other (the two tiles
+// together would hold twice the activations in registers: k_rollout then spills to scratch).
+// Every lane of the wave calls it (wave-uniform control flow): x = this lane's env's row (x[19] = 0
+// when in_dim is 19), lds = the staged blob.  Returns the lane's env's six pre-tanh outputs in y
+// and its actions in act.
+__device__ __forceinline__ void actor_wave(const ActorK &ak, const char *lds, const float x[20], float act[6], float y[6])
+{
+    const int lane = (int)(threadIdx.x & 63), h = lane >> 5, r = lane & 31;
+    const actor_f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const actor_bf16x8 fzero = {0, 0, 0, 0, 0, 0, 0, 0};
+    #pragma unroll
+    for (int i = 0; i < 6; ++i) y[i] = 0.f;
+    #pragma unroll 1
+    for (int c = 0; c < 2; ++c) {
+        // the input fragments of column tile c: k-step 0 = features 8h + j, k-step 1 = features
+        // 16 + 8h + j (only 16..19 exist), each split into bf16 hi + lo
+        const int src = 32 * c + r;
+        actor_bf16x8 xh[2], xl[2];
+        xh[1] = fzero;
+        xl[1] = fzero;
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float v0 = __shfl(x[j], src), v1 = __shfl(x[8 + j], src);
+            const float v = h ? v1 : v0;
+            const __bf16 hi = (__bf16)v;
+            xh[0][j] = hi;
+            xl[0][j] = (__bf16)(v - (float)hi);
+        }
+        #pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float v1 = __shfl(x[16 + j], src);
+            const float v = h ? 0.f : v1;
+            const __bf16 hi = (__bf16)v;
+            xh[1][j] = hi;
+            xl[1][j] = (__bf16)(v - (float)hi);
+        }
+        // activations: the k-step fragments of up to 256 features
+        actor_bf16x8 hin[2 * ACTOR_TILES], hout[2 * ACTOR_TILES];
+        #pragma unroll
+        for (int s = 0; s < 2 * ACTOR_TILES; ++s) hin[s] = hout[s] = fzero;
+        // layer 1: W1 x_hi + W1 x_lo, the same two fragments
+        {
+            const char *w = lds + ak.w_off[0];
+            const float *bias = reinterpret_cast<const float *>(lds + ak.b_off[0]);
+            #pragma unroll
+            for (int T = 0; T < ACTOR_TILES; ++T) {
+                if (T < ak.tiles[0]) {
+                    const actor_bf16x8 a0 = actor_frag(w, 2 * T, lane), a1 = actor_frag(w, 2 * T + 1, lane);
+                    actor_f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xh[0], zero, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xh[1], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xl[0], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xl[1], acc, 0, 0, 0);
+                    actor_activate(acc, bias, T, h, hin[2 * T], hin[2 * T + 1]);
+                }
+            }
+        }
+        // the further hidden layers
+        #pragma unroll
+        for (int l = 1; l < CTR_ACTOR_MAX_HIDDEN; ++l) {
+            if (l < ak.n_hidden) {
+                const char *w = lds + ak.w_off[l];
+                const float *bias = reinterpret_cast<const float *>(lds + ak.b_off[l]);
+                const int tin = ak.tiles[l - 1];
+                #pragma unroll
+                for (int T = 0; T < ACTOR_TILES; ++T) {
+                    if (T < ak.tiles[l]) {
+                        actor_f32x16 acc = zero;
+                        #pragma unroll
+                        for (int t = 0; t < ACTOR_TILES; ++t) {
+                            if (t < tin) {
+                                #pragma unroll
+                                for (int s = 2 * t; s < 2 * t + 2; ++s)
+                                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(actor_frag(w, T * 2 * tin + s, lane), hin[s],
+                                                                                  acc, 0, 0, 0);
+                            }
+                        }
+                        actor_activate(acc, bias, T, h, hout[2 * T], hout[2 * T + 1]);
+                    }
+                }
+                #pragma unroll
+                for (int s = 0; s < 2 * ACTOR_TILES; ++s) hin[s] = hout[s];
+            }
+        }
+        // the output layer: one tile, rows 0..5; its bias is added before the lanes move
+        actor_f32x16 acc = zero;
+        {
+            const int lo = ak.n_hidden;               // 1..3: the offsets by constant index
+            const uint32_t wo = lo == 1 ? ak.w_off[1] : (lo == 2 ? ak.w_off[2] : ak.w_off[3]);
+            const uint32_t bo = lo == 1 ? ak.b_off[1] : (lo == 2 ? ak.b_off[2] : ak.b_off[3]);
+            const int tin = lo == 1 ? ak.tiles[0] : (lo == 2 ? ak.tiles[1] : ak.tiles[2]);
+            const char *w = lds + wo;
+            #pragma unroll
+            for (int t = 0; t < ACTOR_TILES; ++t) {
+                if (t < tin) {
+                    #pragma unroll
+                    for (int s = 2 * t; s < 2 * t + 2; ++s)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(actor_frag(w, s, lane), hin[s], acc, 0, 0, 0);
+                }
+            }
+            const float4 bb = *reinterpret_cast<const float4 *>(lds + bo + 16 * h);
+            acc[0] += bb.x;
+            acc[1] += bb.y;
+            acc[2] += bb.z;
+            acc[3] += bb.w;
+        }
+        // rows 0..3 of env 32c + r sit on lane r, rows 4..5 on lane 32 + r; the env's own lane is
+        // lane 32c + r
+        #pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const float v = __shfl(acc[i & 3], i < 4 ? r : 32 + r);
+            y[i] = h == c ? v : y[i];
+        }
+    }
+    #pragma unroll
+    for (int i = 0; i < 6; ++i) act[i] = ak.scale[i] * tanhf(y[i]);
+}

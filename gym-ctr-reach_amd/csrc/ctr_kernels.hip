@@ -628,6 +628,12 @@ struct StepCarry {
     int32_t t;
     uint32_t ep;
     double dg[3];
+    // what k_rollout takes from the step besides: the observation the step leaves (after a reset:
+    // the new episode's), and the step's done, success, error and clock (its statistics)
+    double obs[14], ag[3];   // (ag: filled by step_one)
+    bool done, success;
+    float error;
+    int32_t t_step;
 };
 
 // t_prev, epoch, dg_prev: the env's clock, reset count and desired goal before the step (loaded
@@ -737,6 +743,12 @@ __device__ __forceinline__ void step_finish(const KCfg &kc, const ctr_batch_t &b
         nx->t = t_out;
         #pragma unroll
         for (int i = 0; i < 3; ++i) nx->dg[i] = dg[i];
+        #pragma unroll
+        for (int i = 0; i < 14; ++i) nx->obs[i] = obs[i];
+        nx->done = done;
+        nx->success = d < tol;
+        nx->error = (float)d;
+        nx->t_step = t;
     }
 }
 
@@ -924,15 +936,18 @@ __device__ __forceinline__ float (*next_action_lds())[BLOCK]
 // next_actions (NULL after the last step), whose load is issued before the FK and parked in LDS
 // across it (not in registers the FK loop would have to keep, like the finish's inputs).
 // QUEUE = false (k_step_tail): a pooled reset is not appended to the refill queue.
-template <int MODE, bool HER, bool MANY, bool QUEUE = true>
+// ACTOR (k_rollout, with MANY): r.a holds the action the actor gave for this step and there is no
+// next_actions; on return *seen holds what the actor and the statistics take from the step.
+template <int MODE, bool HER, bool MANY, bool QUEUE = true, bool ACTOR = false>
 __device__ __forceinline__ void step_one(const KCfg &kc, const ctr_batch_t &b, const float *__restrict__ actions,
                                          const ctr_step_out_t &o, int32_t autoreset, const ctr_her_t *her,
                                          const SysK *s_sys, const ctr_tube_raw_t *s_raw, int64_t e, int j, bool in,
                                          bool live, StepRows &r, const ctr_gather_push_t *gp, bool slot_free0,
-                                         const float *__restrict__ next_actions)
+                                         const float *__restrict__ next_actions, StepCarry *seen = nullptr)
 {
     constexpr bool GROUP = (MODE & 6) == 6;
     static_assert(!MANY || (!GROUP && !HER), "k_step_many: one env per lane, no HER");
+    static_assert(!ACTOR || MANY, "k_rollout: the period kernel's step");
     // one env per lane: the finish's inputs wait out the FK in LDS (they have landed during the
     // staging), not in registers the FK loop would have to keep
     __shared__ double s_fin_dg[3][BLOCK];
@@ -1024,6 +1039,11 @@ __device__ __forceinline__ void step_one(const KCfg &kc, const ctr_batch_t &b, c
             for (int i = 0; i < 3; ++i) r.dg[i] = nx.dg[i];
             #pragma unroll
             for (int i = 0; i < 6; ++i) { r.q[i] = q[i]; r.a[i] = next_action_lds()[i][threadIdx.x]; }
+        }
+        if constexpr (ACTOR) {
+            *seen = nx;
+            #pragma unroll
+            for (int i = 0; i < 3; ++i) seen->ag[i] = ag[i];     // (the reset's after a pooled reset)
         }
     }
     step_epilogue(b, o, autoreset, fl, e, live, gp, slot_free0, grow, !MANY, QUEUE);
@@ -2683,6 +2703,228 @@ int ctr_step_period(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const
     default: hipLaunchKernelGGL(k_tail_close<5>, gc, blk, shm, s, kc, b); break;
     }
     return hip_check("ctr_step_period close launch");
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// The MLP actor (ctr_actor) and the closed-loop period kernel (ctr_rollout): k_step_many's loop with
+// each step's action computed by the actor from the observation the step before left in the lane's
+// registers.  The blob is staged into LDS with the tables (the staging's one barrier); after it no
+// wave waits for another, as in k_step_many.
+namespace {
+
+#include "ctr_actor.inc"
+
+__global__ __launch_bounds__(BLOCK) void k_actor(ActorK ak, const float *__restrict__ rows, int64_t n,
+                                                 float *__restrict__ actions, float *__restrict__ logits)
+{
+    char *lds = actor_lds_base(0);
+    actor_stage(ak, lds);
+    const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const float *row = rows + (e < n ? e : n - 1) * ak.in_dim;     // lanes past n: the clamped row, no write
+    float x[20];
+    #pragma unroll
+    for (int k = 0; k < 19; ++k) x[k] = row[k];
+    x[19] = ak.in_dim == 20 ? row[19] : 0.f;
+    __syncthreads();
+    float a[6], y[6];
+    actor_wave(ak, lds, x, a, y);
+    if (e < n) {
+        #pragma unroll
+        for (int i = 0; i < 6; ++i) actions[6 * e + i] = a[i];
+        if (logits)
+            #pragma unroll
+            for (int i = 0; i < 6; ++i) logits[6 * e + i] = y[i];
+    }
+}
+
+template <int MODE>
+__device__ __forceinline__ void step_body_rollout(const KCfg &kc, const ctr_batch_t &b, const ActorK &ak, int32_t k,
+                                                  const ctr_step_out_t &o, int32_t autoreset,
+                                                  const ctr_rollout_aux_t &aux)
+{
+    __shared__ SysK s_sys[CTR_MAX_SYSTEMS];
+    __shared__ ctr_tube_raw_t s_raw[CTR_MAX_SYSTEMS];
+    const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool live = e < b.n;
+    const int64_t ec = live ? e : b.n - 1;
+    const bool multi = kc.c.n_systems > 1;
+    StageRegs stg;
+    stage_load(kc, stg);
+    __builtin_amdgcn_sched_barrier(0);       // keep the table loads ahead of the row loads
+    StepRows r;
+    r.s = b.system[ec];
+    #pragma unroll
+    for (int i = 0; i < 6; ++i) { r.q[i] = b.joints[6 * ec + i]; r.a[i] = 0.f; }
+    r.t = b.t[ec];
+    r.ep = b.epoch[ec];
+    #pragma unroll
+    for (int i = 0; i < 3; ++i) r.dg[i] = b.desired_goal[3 * ec + i];
+    // step 0's row from memory: the observation the last call left, rounded as write_obs rounds
+    float x[20];
+    {
+        const int od = multi ? 14 : 13;
+        float ob[14], ag[3], dg[3];
+        if (kc.c.obs_f64) {
+            const double *src = static_cast<const double *>(o.obs) + od * ec;
+            #pragma unroll
+            for (int i = 0; i < 13; ++i) ob[i] = (float)src[i];
+            ob[13] = multi ? (float)src[13] : 0.f;
+        } else {
+            const float *src = static_cast<const float *>(o.obs) + od * ec;
+            #pragma unroll
+            for (int i = 0; i < 13; ++i) ob[i] = src[i];
+            ob[13] = multi ? src[13] : 0.f;
+        }
+        #pragma unroll
+        for (int i = 0; i < 3; ++i) { ag[i] = (float)b.achieved_goal[3 * ec + i]; dg[i] = (float)r.dg[i]; }
+        actor_row(ob, ag, dg, multi, x);
+    }
+    char *lds = actor_lds_base(lane_lds_bytes(kc));
+    actor_stage(ak, lds);
+    stage_systems<true>(kc, s_sys, s_raw, &stg);
+    if (autoreset == CTR_AUTORESET_POOLED && blockIdx.x == 0 && threadIdx.x == 0) {   // as k_step_many
+        b.work[(b.work_parity & 1) ^ 1] = 0;
+        if (k > 1) b.work[b.work_parity & 1] = 0;
+    }
+    #pragma unroll 1
+    for (int32_t i = 0; i < k; ++i) {
+        float y[6];
+        actor_wave(ak, lds, x, r.a, y);       // every lane of the wave, outside the live region
+        if (aux.actions && live)
+            #pragma unroll
+            for (int j = 0; j < 6; ++j) aux.actions[((int64_t)i * b.n + e) * 6 + j] = r.a[j];
+        StepCarry seen = {};                  // (lanes past n: a zero row from the second step on)
+        step_one<MODE, false, true, true, true>(kc, b, nullptr, o, autoreset, nullptr, s_sys, s_raw, e, 0, live, live, r,
+                                                nullptr, true, nullptr, &seen);
+        // the next step's row from the registers the step left, rounded as write_obs rounds (every
+        // lane: the row is not carried across the step)
+        {
+            float ob[14], ag[3], dg[3];
+            obs_to_f32(seen.obs, ob);
+            #pragma unroll
+            for (int j = 0; j < 3; ++j) { ag[j] = (float)seen.ag[j]; dg[j] = (float)seen.dg[j]; }
+            actor_row(ob, ag, dg, multi, x);
+        }
+        if (live) {
+            // the statistics: this env's own rows, only in a step it is done in
+            if (seen.done) {
+                if (aux.episodes) aux.episodes[e] += 1u;
+                if (aux.successes) aux.successes[e] += seen.success ? 1u : 0u;
+                if (aux.error_sum) aux.error_sum[e] += (double)seen.error;
+                if (aux.length_sum) aux.length_sum[e] += (uint32_t)seen.t_step;
+            }
+        }
+    }
+}
+
+// (MODE 1, the compliant model's scipy RK45 with a y pre-curvature, would spill to scratch -- its
+// k_step_many already fills the register file -- and is refused by ctr_rollout, as by ctr_step_period)
+template <int MODE>
+constexpr bool rollout_mode() { return !pair_mode<MODE>() && (MODE & 6) != 6 && MODE != 1; }
+
+template <int MODE>
+__global__ __launch_bounds__(BLOCK) void k_rollout(KCfg kc, ctr_batch_t b, ActorK ak, int32_t k, ctr_step_out_t o,
+                                                   int32_t autoreset, ctr_rollout_aux_t aux)
+{
+    if constexpr (rollout_mode<MODE>()) step_body_rollout<MODE>(kc, b, ak, k, o, autoreset, aux);
+}
+
+// LDS of a workgroup on gfx950, and the static LDS of k_rollout<MODE> (the build's resource-usage
+// remarks): what the blob and the domain tables share the rest with.
+constexpr size_t LDS_PER_WORKGROUP = 160 * 1024;
+constexpr size_t ROLLOUT_STATIC_LDS[6] = {78976, 0, 0, 90240, 78976, 78976};
+
+// a launch with more than 64 KB of dynamic LDS says so first (per device and kernel: a host call
+// of about a microsecond, not worth a table of what has been said where)
+template <typename K>
+int allow_dynamic_lds(K kernel, size_t bytes)
+{
+    if (bytes <= 64 * 1024) return 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)bytes) != hipSuccess)
+        return hip_check("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t ctr_actor_blob_bytes(const ctr_actor_t *a)
+{
+    ActorK ak;
+    if (actor_layout(a, &ak)) return -1;
+    return (int64_t)ak.bytes;
+}
+
+int ctr_actor_pack(const ctr_actor_t *a, const float *const *W, const float *const *b, void *blob_host)
+{
+    return actor_pack(a, W, b, blob_host);
+}
+
+int ctr_actor(const ctr_actor_t *a, const float *rows, int64_t n, float *actions, float *logits, void *stream)
+{
+    ActorK ak;
+    if (int r = actor_check(a, &ak)) return r;
+    if (n < 0 || n > 0x7fffffff) return fail(CTR_EINVAL, "ctr_actor: n out of range");
+    if (n > 0 && (!rows || !actions)) return fail(CTR_EINVAL, "ctr_actor: rows or actions is NULL");
+    if (n == 0) return 0;
+    const size_t shm = ak.bytes + ACTOR_LDS_SLACK;
+    if (int r = allow_dynamic_lds(k_actor, shm)) return r;
+    hipLaunchKernelGGL(k_actor, dim3(grid_for(n)), dim3(BLOCK), shm, (hipStream_t)stream, ak, rows, n, actions, logits);
+    return hip_check("ctr_actor launch");
+}
+
+int ctr_rollout(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *actor, int32_t k,
+                const ctr_step_out_t *out, int32_t autoreset, const ctr_rollout_aux_t *aux, void *stream)
+{
+    if (int r = check_cfg(cfg)) return r;
+    ActorK ak;
+    if (int r = actor_check(actor, &ak)) return r;
+    if (ak.in_dim != (cfg->n_systems > 1 ? 14 : 13) + 6)
+        return fail(CTR_EINVAL, "ctr_rollout: actor->in_dim must be obs_dim + 6 (19 for one system, 20 for several)");
+    // ctr_step_many's eligibility, with its messages (its action table: k placeholders, never read)
+    KCfg kc;
+    ctr_action_seq_t seq, unused;
+    for (int32_t i = 0; i < CTR_STEP_MANY_MAX; ++i) seq.a[i] = reinterpret_cast<const float *>(sizeof(float));
+    if (int r = step_many_check(cfg, batch, &seq, k, out, autoreset, &kc, &unused)) return r;
+    const ctr_rollout_aux_t ax = aux ? *aux : ctr_rollout_aux_t{};
+    if ((ax.episodes || ax.successes || ax.error_sum || ax.length_sum) && autoreset != CTR_AUTORESET_POOLED)
+        return fail(CTR_EINVAL, "ctr_rollout: the episode statistics need CTR_AUTORESET_POOLED (without auto-reset a done "
+                                "environment stays done)");
+    const ctr_batch_t b = *batch;
+    const ctr_step_out_t o = *out;
+    if (b.n == 0) return 0;
+    if (kc.mode == 1)
+        return fail(CTR_EINVAL, "ctr_rollout: not for the compliant model's scipy RK45 with y pre-curvature (the kernel "
+                                "would spill to scratch); use ctr_actor + ctr_step");
+    const size_t lane = lane_lds_bytes(kc), fixed = ROLLOUT_STATIC_LDS[kc.mode < 6 ? kc.mode : 0];
+    const size_t shm = lane + ak.bytes + ACTOR_LDS_SLACK;
+    if (fixed + shm > LDS_PER_WORKGROUP) {
+        snprintf(g_err, sizeof g_err, "ctr_rollout: the actor's blob (%u B) + the kernel's static LDS (%zu B) + the domain "
+                 "randomisation tables (%zu B) exceed the %zu B of LDS of a workgroup; use ctr_actor + ctr_step",
+                 ak.bytes, fixed, lane, LDS_PER_WORKGROUP);
+        return CTR_EINVAL;
+    }
+    const dim3 g(grid_for(b.n)), blk(BLOCK);
+    hipStream_t s = (hipStream_t)stream;
+#define CTR_ROLLOUT_CASE(M)                                                                           \
+    case M:                                                                                           \
+        if (int r = allow_dynamic_lds(k_rollout<M>, shm)) return r;                          \
+        hipLaunchKernelGGL(k_rollout<M>, g, blk, shm, s, kc, b, ak, k, o, autoreset, ax);             \
+        break;
+    switch (kc.mode) {
+    CTR_ROLLOUT_CASE(0)
+    CTR_ROLLOUT_CASE(2)      // (a build without the lane pairs)
+    CTR_ROLLOUT_CASE(3)
+    CTR_ROLLOUT_CASE(4)
+    default:
+    CTR_ROLLOUT_CASE(5)
+    }
+#undef CTR_ROLLOUT_CASE
+    return hip_check("ctr_rollout launch");
 }
 
 }  // extern "C"

@@ -17,6 +17,9 @@ CTR_MAX_SYSTEMS = 8
 CTR_POOL_MAX = 192          # ctr_batch_t.pool_depth limit
 CTR_STEP_MANY_MAX = 64      # steps of one ctr_step_many launch
 CTR_IK_MAX_ITERS = 8192     # waypoints * num of one ctr_ik_dls launch
+CTR_ACTOR_MAX_HIDDEN = 3    # hidden layers of an MLP actor
+CTR_ACTOR_MAX_WIDTH = 256   # widest hidden layer
+CTR_ACTOR_MAX_BYTES = 98304  # largest packed actor (it is staged into LDS)
 CTR_HER_SCAN_TILE = 1024
 CTR_INTEGRATOR_RK45_SCIPY = 0
 CTR_INTEGRATOR_RK4 = 1
@@ -149,6 +152,18 @@ class CtrIk(ctypes.Structure):
                 ("targets", _P), ("q0", _P), ("sys_idx", _P), ("q", _P), ("err", _P), ("iters", _P), ("status", _P)]
 
 
+class CtrActor(ctypes.Structure):
+    """ctr_actor_t: an MLP actor and its packed device blob (added within ABI 17)."""
+    _fields_ = [("in_dim", ctypes.c_int32), ("n_hidden", ctypes.c_int32),
+                ("width", ctypes.c_int32 * CTR_ACTOR_MAX_HIDDEN), ("pad", ctypes.c_int32),
+                ("scale", ctypes.c_float * 6), ("blob", _P)]
+
+
+class CtrRolloutAux(ctypes.Structure):
+    """ctr_rollout_aux_t: ctr_rollout's recorded actions and per-env episode statistics."""
+    _fields_ = [("actions", _P), ("episodes", _P), ("successes", _P), ("error_sum", _P), ("length_sum", _P)]
+
+
 class CtrGatherPush(ctypes.Structure):
     _fields_ = [("src", _P), ("n", ctypes.c_int64), ("world", ctypes.c_int32), ("pad", ctypes.c_int32),
                 ("dst", _P * CTR_GATHER_MAX_RANKS), ("seqw", _P * CTR_GATHER_MAX_RANKS), ("ticket", _P),
@@ -201,7 +216,7 @@ EXPORTED = ("ctr_abi_version", "ctr_last_error", "ctr_fk", "ctr_set_action", "ct
             "ctr_her_open", "ctr_her_record", "ctr_her_sample", "ctr_step_her", "ctr_pool_requeue",
             "ctr_ipc_get_handle", "ctr_ipc_open", "ctr_ipc_close", "ctr_seqw_alloc", "ctr_seqw_free", "ctr_copy_list",
             "ctr_gather_wait", "ctr_gather_push", "ctr_gather_publish", "ctr_refill_carry_bytes", "ctr_step_many",
-            "ctr_ik_dls", "ctr_step_period")
+            "ctr_ik_dls", "ctr_step_period", "ctr_actor_blob_bytes", "ctr_actor_pack", "ctr_actor", "ctr_rollout")
 
 _lib = None
 
@@ -263,6 +278,13 @@ def load(path=None):
     if hasattr(L, "ctr_step_period"):              # added within ABI 17 (an older build lacks it)
         L.ctr_step_period.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch),
                                       ctypes.POINTER(CtrActionSeq), i32, ctypes.POINTER(CtrStepOut), _P]
+    if hasattr(L, "ctr_actor"):                    # added within ABI 17 (an older build lacks them)
+        L.ctr_actor_blob_bytes.argtypes = [ctypes.POINTER(CtrActor)]
+        L.ctr_actor_blob_bytes.restype = i64
+        L.ctr_actor_pack.argtypes = [ctypes.POINTER(CtrActor), ctypes.POINTER(_P), ctypes.POINTER(_P), _P]
+        L.ctr_actor.argtypes = [ctypes.POINTER(CtrActor), _P, i64, _P, _P, _P]
+        L.ctr_rollout.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch), ctypes.POINTER(CtrActor), i32,
+                                  ctypes.POINTER(CtrStepOut), i32, ctypes.POINTER(CtrRolloutAux), _P]
     if hasattr(L, "ctr_ik_dls"):                   # ABI 17
         L.ctr_ik_dls.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrIk), _P]
     if hasattr(L, "ctr_refill_carry_bytes"):       # ABI 12

@@ -1,0 +1,154 @@
+"""A deterministic MLP actor on the device (ctr_actor / ctr_rollout, include/ctr_reach_amd.h): the
+reference's stable-baselines DDPG ``MlpPolicy`` actor on HERGoalEnvWrapper's flat row
+``[observation, achieved_goal, desired_goal]``.
+
+    actor = MlpActor([(W1, b1), (W2, b2), (Wout, bout)], scale=venv.action_space.high, device="cuda")
+    actions = venv.act(actor)                 # one ctr_actor launch
+    venv.rollout(actor, 20)                   # 20 closed-loop steps, one launch per refill period
+
+``MlpActor.emulate`` is the CPU reference of the actor's arithmetic (numpy, no GPU, no library).
+"""
+import numpy as np
+
+from . import _abi
+
+
+def bf16_round(x):
+    """float32 values rounded to bfloat16 (nearest even), as float32.  NaN stays NaN."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    u = x.view(np.uint32)
+    r = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)).view(np.float32)
+    return np.where(np.isnan(x), np.float32(np.nan), r).astype(np.float32)
+
+
+class MlpActor(object):
+    """``layers``: [(W, b), ...] numpy arrays or torch tensors in torch's [out, in] convention, 1..3
+    hidden layers (widths multiples of 32, at most 256) and the 6-row output layer; the first
+    layer takes the flat row of obs_dim + 6 = 19 or 20 floats.  ``scale``: the action space's high
+    (6 floats): action = scale * tanh(output).  ``device`` None keeps the actor on the host
+    (``emulate`` only)."""
+
+    def __init__(self, layers, scale, device=None):
+        ws, bs = [], []
+        for W, b in layers:
+            ws.append(np.ascontiguousarray(_to_numpy(W), dtype=np.float32))
+            bs.append(np.ascontiguousarray(_to_numpy(b), dtype=np.float32).reshape(-1))
+        if not 2 <= len(ws) <= _abi.CTR_ACTOR_MAX_HIDDEN + 1:
+            raise ValueError("an actor has 1..%d hidden layers and an output layer" % _abi.CTR_ACTOR_MAX_HIDDEN)
+        for l, (W, b) in enumerate(zip(ws, bs)):
+            if W.ndim != 2 or b.shape != (W.shape[0],):
+                raise ValueError("layer %d: W must be [out, in] and b [out]" % l)
+            if l and W.shape[1] != ws[l - 1].shape[0]:
+                raise ValueError("layer %d takes %d inputs, layer %d gives %d" % (l, W.shape[1], l - 1, ws[l - 1].shape[0]))
+        if ws[0].shape[1] not in (19, 20):
+            raise ValueError("the first layer takes the flat row of obs_dim + 6 = 19 or 20 floats")
+        if ws[-1].shape[0] != 6:
+            raise ValueError("the output layer has 6 rows (the actions)")
+        for W in ws[:-1]:
+            if W.shape[0] % 32 or not 32 <= W.shape[0] <= _abi.CTR_ACTOR_MAX_WIDTH:
+                raise ValueError("hidden widths must be multiples of 32 in 32..%d" % _abi.CTR_ACTOR_MAX_WIDTH)
+        self.weights, self.biases = ws, bs
+        self.in_dim = ws[0].shape[1]
+        self.hidden = [W.shape[0] for W in ws[:-1]]
+        self.scale = np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
+        if self.scale.shape != (6,) or not np.isfinite(self.scale).all():
+            raise ValueError("scale must be 6 finite floats")
+        self.device = None
+        self.blob = None
+        self._struct = _abi.CtrActor()
+        s = self._struct
+        s.in_dim, s.n_hidden = self.in_dim, len(self.hidden)
+        for l, w in enumerate(self.hidden):
+            s.width[l] = w
+        for i in range(6):
+            s.scale[i] = float(self.scale[i])
+        if device is not None:
+            self._upload(device)
+
+    @classmethod
+    def from_torch(cls, seq, scale, device=None):
+        """From an ``nn.Sequential`` of Linear, ReLU, ..., Linear, Tanh."""
+        import torch.nn as nn
+        mods = list(seq)
+        if not mods or not isinstance(mods[-1], nn.Tanh):
+            raise ValueError("the actor ends with nn.Tanh")
+        layers = []
+        for i, m in enumerate(mods[:-1]):
+            if i % 2 == 0:
+                if not isinstance(m, nn.Linear) or m.bias is None:
+                    raise ValueError("module %d must be an nn.Linear with a bias" % i)
+                layers.append((m.weight.detach(), m.bias.detach()))
+            elif not isinstance(m, nn.ReLU):
+                raise ValueError("module %d must be an nn.ReLU" % i)
+        if len(mods) % 2:
+            raise ValueError("expected Linear, ReLU, ..., Linear, Tanh")
+        return cls(layers, scale, device)
+
+    def _upload(self, device):
+        import torch
+        lib = _abi.load()
+        nb = int(lib.ctr_actor_blob_bytes(self._struct))
+        if nb < 0:
+            raise _abi.CtrError("ctr_actor_blob_bytes: " + lib.ctr_last_error().decode())
+        host = np.zeros(nb, dtype=np.uint8)
+        n = len(self.weights)
+        W = (_abi._P * n)(*[w.ctypes.data for w in self.weights])
+        b = (_abi._P * n)(*[v.ctypes.data for v in self.biases])
+        _abi.check(lib.ctr_actor_pack(self._struct, W, b, host.ctypes.data), "ctr_actor_pack")
+        self.packed = host
+        self.device = torch.device(device)
+        self.blob = torch.from_numpy(host).to(self.device)
+        if self.blob.data_ptr() % 16:
+            raise RuntimeError("actor blob not 16-B aligned")
+        self._struct.blob = self.blob.data_ptr()
+
+    def emulate(self, rows):
+        """The actor's arithmetic (include/ctr_reach_amd.h) in numpy float64 with the kernel's bf16
+        roundings: rows [n, in_dim] -> (actions [n, 6], logits [n, 6]) float64.  Also returns the
+        intermediates in ``self.last_hidden`` (the bf16 activations of every hidden layer)."""
+        x = np.asarray(rows, dtype=np.float32).reshape(-1, self.in_dim)
+        with np.errstate(invalid="ignore", over="ignore"):
+            hi = bf16_round(x)
+            lo = bf16_round(x - hi)
+            Wq = [bf16_round(W).astype(np.float64) for W in self.weights]
+            z = hi.astype(np.float64) @ Wq[0].T + lo.astype(np.float64) @ Wq[0].T
+            self.last_hidden = []
+            for l in range(len(self.hidden)):
+                z = (z.astype(np.float32) + self.biases[l]).astype(np.float32)      # f32 result + f32 bias
+                h = bf16_round(np.where(z > 0, z, np.float32(0)))
+                self.last_hidden.append(h)
+                z = h.astype(np.float64) @ Wq[l + 1].T
+            y = z + self.biases[-1].astype(np.float64)
+            return self.scale.astype(np.float64) * np.tanh(y), y
+
+    def reference(self, rows):
+        """The plain float64 MLP (no bf16 anywhere): actions [n, 6]."""
+        z = np.asarray(rows, dtype=np.float64).reshape(-1, self.in_dim)
+        for l, (W, b) in enumerate(zip(self.weights, self.biases)):
+            z = z @ W.astype(np.float64).T + b.astype(np.float64)
+            if l < len(self.hidden):
+                z = np.maximum(z, 0.0)
+        return self.scale.astype(np.float64) * np.tanh(z)
+
+    def __call__(self, rows, logits=False, stream=None):
+        """ctr_actor: rows [n, in_dim] float32 device tensor -> actions [n, 6] (and the pre-tanh
+        outputs with ``logits``)."""
+        import torch
+        if self.blob is None:
+            raise RuntimeError("the actor is on the host (MlpActor(..., device=None))")
+        rows = rows.to(device=self.device, dtype=torch.float32).contiguous()
+        if rows.dim() != 2 or rows.shape[1] != self.in_dim:
+            raise ValueError("rows must be [n, %d]" % self.in_dim)
+        n = rows.shape[0]
+        act = torch.empty((n, 6), dtype=torch.float32, device=self.device)
+        lg = torch.empty((n, 6), dtype=torch.float32, device=self.device) if logits else None
+        rc = _abi.load().ctr_actor(self._struct, _abi.ptr(rows), n, _abi.ptr(act), _abi.ptr(lg),
+                                   _abi.stream_ptr(stream, self.device.index))
+        _abi.check(rc, "ctr_actor")
+        return (act, lg) if logits else act
+
+
+def _to_numpy(t):
+    if hasattr(t, "detach"):
+        return t.detach().cpu().numpy()
+    return np.asarray(t)

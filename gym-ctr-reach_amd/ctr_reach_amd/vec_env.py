@@ -522,6 +522,88 @@ class CtrReachVecEnv(object):
                     self.refill_pool(stream)
             i += k
 
+    # ------------------------------------------------------------------ closed loop (policy.MlpActor)
+    def actor_rows(self):
+        """The flat rows an actor reads: [observation, achieved_goal, desired_goal] as float32
+        [N, obs_dim + 6] (HERGoalEnvWrapper's layout) of the env's current observation."""
+        torch = _torch()
+        return torch.cat((self.obs.to(torch.float32), self.achieved_goal.to(torch.float32),
+                          self.desired_goal.to(torch.float32)), dim=1)
+
+    def act(self, actor, stream=None):
+        """The actor's actions on the env's current observation: [N, 6] float32 (one ctr_actor
+        launch)."""
+        if actor.in_dim != self.obs_dim + 6:
+            raise ValueError("the actor takes %d inputs, this env's rows have %d" % (actor.in_dim, self.obs_dim + 6))
+        return actor(self.actor_rows(), stream=stream)
+
+    ROLLOUT_STATS = (("episodes", "int32"), ("successes", "int32"), ("error_sum", "float64"), ("length_sum", "int32"))
+
+    def reset_rollout_stats(self):
+        """Zero ``rollout_stats`` (allocating them on first use): per-env episodes finished inside
+        rollout(), their successes, the sum of their final errors and of their lengths."""
+        torch = _torch()
+        if getattr(self, "rollout_stats", None) is None:
+            self.rollout_stats = {k: torch.zeros(self.num_envs, dtype=getattr(torch, dt), device=self.device)
+                                  for k, dt in self.ROLLOUT_STATS}
+        else:
+            for v in self.rollout_stats.values():
+                v.zero_()
+        return self.rollout_stats
+
+    def rollout(self, actor, steps, record_actions=False, stream=None):
+        """``steps`` closed-loop steps, action = actor(observation), each refill period's steps as
+        one launch (ctr_rollout: the actor runs inside the fused period kernel).  The state, the
+        outputs and the host bookkeeping afterwards are those of ``steps`` rounds of
+        ``step_raw(act(actor))``, bit for bit; the launches split at refill boundaries and the
+        refills run between them exactly as in step_many, which also says which envs are eligible
+        (RuntimeError otherwise).  With auto-reset the per-env episode statistics accumulate in
+        ``rollout_stats``.  Returns the applied actions [steps, N, 6] with ``record_actions``."""
+        torch = _torch()
+        why = self.step_many_ineligible()
+        if why:
+            raise RuntimeError("rollout: " + why)
+        if not self._tail_eligible():          # ctr_rollout refuses that mode as ctr_step_period does
+            raise RuntimeError("rollout: not for the compliant model's scipy RK45 with y pre-curvature (the kernel "
+                               "would spill to scratch); use act() and step_raw()")
+        if actor.blob is None or actor.blob.device != self.obs.device:
+            raise ValueError("rollout: the actor must be on %s" % self.device)
+        if actor.in_dim != self.obs_dim + 6:
+            raise ValueError("the actor takes %d inputs, this env's rows have %d" % (actor.in_dim, self.obs_dim + 6))
+        steps = int(steps)
+        rec = torch.empty((steps, self.num_envs, 6), dtype=torch.float32, device=self.device) if record_actions else None
+        aux = _abi.CtrRolloutAux()
+        if self.autoreset:
+            if getattr(self, "rollout_stats", None) is None:
+                self.reset_rollout_stats()
+            for k, _ in self.ROLLOUT_STATS:
+                setattr(aux, k, self.rollout_stats[k].data_ptr())
+        self.cfg.tol = float(self.goal_tolerance.get_tol())
+        sp = _abi.stream_ptr(stream, self.device.index)
+        i = 0
+        while i < steps:
+            k = min(steps - i, _abi.CTR_STEP_MANY_MAX)
+            if self.pool_depth:                # never past the refill that falls due
+                k = min(k, self.refill_interval - self._steps_since_refill)
+            mode = _abi.AUTORESET_OFF
+            if self.autoreset:                 # every step of the launch as step_raw would run it: POOLED
+                k = min(k, self._pooled_steps() - self._steps_since_refill)
+                if k < 1 or not self._pool_full:
+                    raise RuntimeError("rollout: the next step's resets are not all in the pool")
+                mode = _abi.AUTORESET_POOLED
+            aux.actions = rec[i].data_ptr() if rec is not None else None
+            rc = self.lib.ctr_rollout(self.cfg, self._batch, actor._struct, k, self._out, mode, aux, sp)
+            _abi.check(rc, "ctr_rollout")
+            self.fused_launches += 1
+            if self.autoreset and k % 2:
+                self._batch.work_parity ^= 1
+            if self.pool_depth:
+                self._steps_since_refill += k
+                if self._steps_since_refill >= self.refill_interval:
+                    self.refill_pool(stream)
+            i += k
+        return rec
+
     def capture_steps(self, actions, stream=None):
         """Capture len(actions) consecutive steps (step_raw, with the pool refills that fall due)
         into one HIP graph; ``StepGraph.replay()`` then runs them with a single launch, so a

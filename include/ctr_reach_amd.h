@@ -29,6 +29,10 @@
  *   ctr_jacobian        CTR_Model.jac (finite differences)             envs/CTR_Python/CTR_Model.py:251-262
  *   ctr_ik_dls          dls_ik_position_only(model, q0, P_d, lam, num, tol) src/jacobian_controller.py:19-73
  *                       (and its use along the line / circle / helix waypoint paths of src/)
+ *   ctr_actor / ctr_rollout
+ *                       model.predict(obs, deterministic=True) of the stable-baselines DDPG MlpPolicy
+ *                       actor in the evaluation loops of src/ (the loops behind evaluations*.csv),
+ *                       ctr_rollout together with the env.step calls of those loops
  *   ctr_domain_params   Model.current_sys_parameters after randomize_parameters
  *                                                                          envs/model.py:20-28, model_utils.py:5-35
  *   ctr_her_open / ctr_her_record / ctr_her_sample
@@ -466,6 +470,79 @@ int ctr_step_many(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const c
  * register file without scratch; use ctr_step_many and ctr_pool_refill).  Stream-ordered; nothing is allocated. */
 int ctr_step_period(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_action_seq_t *actions,
                     int32_t k, const ctr_step_out_t *out, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * MLP actor (entry points added within ABI 17: no existing entry point or struct changes, so the
+ * number stays; a caller that needs them looks the symbols up).  A deterministic policy on the
+ * device: the reference's stable-baselines DDPG MlpPolicy actor on HERGoalEnvWrapper's flat row
+ * x = [observation, achieved_goal, desired_goal] (in_dim = obs_dim + 6 floats, the layout of
+ * ctr_her_batch_t.obs).  1..3 hidden layers, widths multiples of 32 up to 256:
+ *     x_hi = bf16(x);  x_lo = bf16(x - float(x_hi))        (round to nearest even; x - x_hi in f32)
+ *     z1   = W1 x_hi + W1 x_lo                             (bf16 weights, f32 accumulation)
+ *     h1   = bf16(relu(z1 + b1))                           (f32 bias; relu(z) = z > 0 ? z : 0)
+ *     hl   = bf16(relu(Wl h(l-1) + bl))                    the further hidden layers
+ *     y    = Wout hL + bout                                6 "logits", f32
+ *     a_i  = scale_i * tanhf(y_i)
+ * An env's action depends on its own row and the weights only (not on n or on its neighbours).
+ * The weights live in one packed device blob (ctr_actor_pack), staged into LDS once per launch:
+ * per layer l = 0..n_hidden (the last one the 6-row output layer, padded to 32 rows), per 32-row
+ * tile T, per k-step S (2 for layer 0, whose in_dim inputs are padded to 32; width[l-1] / 16 after),
+ * 64 lane fragments of 8 bf16 (16 B each): fragment (T, S, lane) starts at byte
+ * w_off[l] + ((T * ksteps + S) * 64 + lane) * 16, w_off[0] = 0, the layers back to back; its element
+ * j is bf16(W[l][32 T + (lane & 31)][k]) (0 past the matrix) with, for h = lane >> 5,
+ *     layer 0:  k = 16 S + 8 h + j
+ *     others:   k = 32 (S >> 1) + 16 (S & 1) + 8 (j >> 2) + 4 h + (j & 3)
+ * (the order in which the matrix cores hand a layer's result to the next).  The f32 biases follow
+ * the last fragment, layer after layer, each padded with zeros to its whole 32-row tiles.
+ * [128,128,128] packs to 81 920 B of weights + 1 664 B of biases, the largest network supported. */
+#define CTR_ACTOR_MAX_HIDDEN 3
+#define CTR_ACTOR_MAX_WIDTH  256
+#define CTR_ACTOR_MAX_BYTES  98304
+typedef struct ctr_actor_t {
+    int32_t in_dim;                 /* obs_dim + 6: 19 or 20                         */
+    int32_t n_hidden;               /* 1..CTR_ACTOR_MAX_HIDDEN                       */
+    int32_t width[CTR_ACTOR_MAX_HIDDEN]; /* multiples of 32, <= CTR_ACTOR_MAX_WIDTH  */
+    int32_t pad;
+    float   scale[6];               /* finite                                        */
+    const void *blob;               /* device, 16-B aligned, ctr_actor_blob_bytes()  */
+} ctr_actor_t;
+
+/* Bytes of the packed blob; -1 on a refused shape (ctr_last_error: which, with the byte counts
+ * where the network exceeds CTR_ACTOR_MAX_BYTES).  scale and blob are not read. */
+int64_t ctr_actor_blob_bytes(const ctr_actor_t *a);
+/* Host only, no HIP call: row-major f32 W[l] [out][in], b[l] [out] (l = 0..n_hidden, the last one
+ * the 6-row output layer) -> the packed blob in host memory, which the caller copies to the
+ * device.  The weights are rounded to bf16 here, once.  scale and blob are not read. */
+int ctr_actor_pack(const ctr_actor_t *a, const float *const *W, const float *const *b, void *blob_host);
+/* rows [n][in_dim] f32 -> actions [n][6] f32; logits [n][6] (the pre-tanh y) or NULL.  (device) */
+int ctr_actor(const ctr_actor_t *a, const float *rows, int64_t n, float *actions, float *logits, void *stream);
+
+/* Closed-loop ctr_step_many: k steps in one launch, each step's action computed by the actor from
+ * the observation the step before left.  Afterwards the batch, the outputs, the pool and the refill
+ * queue are exactly what k rounds of
+ *     row = [(float)out->obs, (float)batch->achieved_goal, (float)batch->desired_goal]
+ *     ctr_actor(actor, row, ...);  ctr_step(cfg, batch, actions, out, autoreset, ...)
+ * with batch->work_parity toggled after every step would have left, bit for bit.  The caller
+ * promises that out->obs holds the batch's current observation (the last call on the batch was
+ * ctr_reset, ctr_step* or ctr_rollout).  The blob is staged into LDS once; no wave waits for another
+ * after that.  aux (NULL, or any of its pointers NULL: not wanted) records the actions and
+ * accumulates per-env episode statistics: each env's lane adds to its own row in every step the
+ * env is done in.
+ * Refused (CTR_EINVAL, before any HIP call) wherever ctr_step_many is, with its messages; when
+ * actor->in_dim != obs_dim + 6; for a refused actor; for the statistics arrays without
+ * CTR_AUTORESET_POOLED (a done env would stay done and be counted at every step); and when the
+ * blob, the kernel's static LDS and the domain-randomisation tables together exceed the 160 KB of
+ * LDS of a workgroup (the message has the byte counts: use ctr_actor + ctr_step there).  n = 0
+ * is a no-op. */
+typedef struct ctr_rollout_aux_t {   /* every pointer device, or NULL */
+    float    *actions;      /* [k][n][6] the action applied in each step                    */
+    uint32_t *episodes;     /* [n] += 1 at every step the env is done in                    */
+    uint32_t *successes;    /* [n] += success of that step                                   */
+    double   *error_sum;    /* [n] += (double)error of that step (the f32 `error` output)    */
+    uint32_t *length_sum;   /* [n] += t of the terminal step                                 */
+} ctr_rollout_aux_t;
+int ctr_rollout(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *actor, int32_t k,
+                const ctr_step_out_t *out, int32_t autoreset, const ctr_rollout_aux_t *aux, void *stream);
 
 /* CtrReachEnv.reset for the environments with mask[i] != 0 (mask NULL = all).
  * goal [n][3] or NULL (sample a goal), system [n] or NULL (sample uniformly).
