@@ -11,7 +11,13 @@
 //                 per-step code k times per wave, no inter-wave wait between the steps
 //   k_step_tail   k_step_many, and each wave then does the period's refill work (suspended resets by
 //                 claim, its own envs' new resets) instead of a k_refill launch; k_tail_close
-//                 follows it and as a rule exits at once (ctr_step_period, at the end of the file)
+//                 follows it and as a rule exits at once (ctr_step_period, near the end of the file)
+//   k_tail_close  finishes the resets k_step_tail's last workgroup found it had to leave (k_refill's code)
+//   k_rollout     k_step_many with each step's action computed by an MLP actor from the observation
+//                 the step before left in the lane's registers (ctr_rollout, at the end of the file)
+//   k_actor       the MLP actor alone, one row per lane, its blob staged into LDS (ctr_actor.inc)
+//   k_ik          the damped-least-squares IK loop and a waypoint path in one launch, 7 lanes of one
+//                 wave per target (ctr_ik_dls)
 //   k_reset       CtrReachEnv.reset, TWO lanes per env (goal FK | start FK in parallel),
 //                 for the queued / masked envs                        (envs/ctr_reach_env.py:70-114)
 //   k_refill      precomputes queued resets into the pool, two lanes per reset
@@ -865,7 +871,7 @@ __device__ __forceinline__ void step_epilogue(const ctr_batch_t &b, const ctr_st
     if (autoreset) {
         if (autoreset == CTR_AUTORESET_POOLED) {
             // no miss sweep follows: zero the next step's miss counter here (this step neither
-            // reads nor appends to either counter; k_step_many has zeroed them for all its steps)
+            // reads nor appends to either counter; a period kernel has zeroed them for all its steps)
             if (zero_miss && blockIdx.x == 0 && threadIdx.x == 0) b.work[(b.work_parity & 1) ^ 1] = 0;
         } else {
             const int32_t one[1] = {(int32_t)e};
@@ -904,13 +910,15 @@ struct StepRows {
 };
 
 // Issues the loads of row ec (unconditional, from a clamped row, so nothing waits for them before
-// the staging).
+// the staging).  ACTION = false (k_rollout, whose actor gives the actions): a zero action row, and
+// actions is not read.
+template <bool ACTION = true>
 __device__ __forceinline__ void step_rows_load(const ctr_batch_t &b, const float *__restrict__ actions, int64_t ec,
                                                StepRows &r)
 {
     r.s = b.system[ec];
     #pragma unroll
-    for (int i = 0; i < 6; ++i) { r.q[i] = b.joints[6 * ec + i]; r.a[i] = actions[6 * ec + i]; }
+    for (int i = 0; i < 6; ++i) { r.q[i] = b.joints[6 * ec + i]; r.a[i] = ACTION ? actions[6 * ec + i] : 0.f; }
     r.t = b.t[ec];
     r.ep = b.epoch[ec];
     #pragma unroll
@@ -924,21 +932,39 @@ __device__ __forceinline__ float (*next_action_lds())[BLOCK]
     return s_next_a;
 }
 
+// What a k_step launch publishes of its own step and of the one before (after the staging).
+__device__ __forceinline__ void step_publish(const ctr_batch_t &b, const ctr_step_out_t &o, const ctr_gather_push_t *gp)
+{
+    // the step's sequence word after the packed rows (the copy-engine gather pushes it after them)
+    if (o.packed && o.packed_seq && blockIdx.x == 0 && threadIdx.x == 0)
+        *reinterpret_cast<uint4 *>(o.packed + 4 * b.n) = make_uint4(o.packed_seq, 0u, 0u, 0u);
+    // fused push gather: the previous gathered step's launch has completed, so its rows are in
+    // every rank's ring (performed at system scope); publish its sequence word there, and release
+    // this rank's slot of step gather_seq + 1 - depth (its readers ran before this launch)
+    if (blockIdx.x == 0) {
+        if (o.gather_prev) gather_publish_lane(o.gather_prev, o.gather_prev_seq);
+        if (gp) gather_release_lane(gp, o.gather_seq + 1u - (uint32_t)gp->depth);
+    }
+}
+
 // One step of the workgroup's envs, after the staging (stage_load, stage_systems: s_sys, s_raw and
 // the trig table are in LDS) and with the step's rows loaded (r): the part k_step runs once and
 // k_step_many once per step of its period.  Nothing in it waits for another wave.
 // Torsionally rigid model with fixed-step RK4 (MODE bits 2 and 4): one env on a group of
 // SEG_GROUP lanes, whose segments run in parallel (fk_group_rigid4); other modes: one env per lane.
-// HER: record the step into the HER store (ctr_step_her); a compile-time switch, so the plain
-// step carries no trace of it (a runtime flag measured +2.3 us on k_step).
-// MANY (k_step_many; one env per lane, no HER, no gather): on return r holds the rows of the
-// env's next step -- the state step_finish left, carried instead of read back, and the row of
-// next_actions (NULL after the last step), whose load is issued before the FK and parked in LDS
-// across it (not in registers the FK loop would have to keep, like the finish's inputs).
-// QUEUE = false (k_step_tail): a pooled reset is not appended to the refill queue.
-// ACTOR (k_rollout, with MANY): r.a holds the action the actor gave for this step and there is no
+// KIND says what the step is a step of; a compile-time switch, so the plain step carries no trace
+// of the others (a runtime HER flag measured +2.3 us on k_step).
+// STEP_HER: record the step into the HER store (ctr_step_her).
+// PERIOD* (MANY below: the period kernels, through PERIOD_STEP; one env per lane, no HER, no
+// gather): on return r holds the rows of the env's next step -- the state step_finish left,
+// carried instead of read back, and the row of next_actions (NULL after the last step), whose load
+// is issued before the FK and parked in LDS across it (not in registers the FK loop would have to
+// keep, like the finish's inputs).
+// PERIOD_TAIL (k_step_tail): a pooled reset is not appended to the refill queue.
+// PERIOD_ROLLOUT (k_rollout): r.a holds the action the actor gave for this step and there is no
 // next_actions; on return *seen holds what the actor and the statistics take from the step.
-template <int MODE, bool HER, bool MANY, bool QUEUE = true, bool ACTOR = false>
+enum StepKind { STEP, STEP_HER, PERIOD, PERIOD_TAIL, PERIOD_ROLLOUT };
+template <int MODE, StepKind KIND>
 __device__ __forceinline__ void step_one(const KCfg &kc, const ctr_batch_t &b, const float *__restrict__ actions,
                                          const ctr_step_out_t &o, int32_t autoreset, const ctr_her_t *her,
                                          const SysK *s_sys, const ctr_tube_raw_t *s_raw, int64_t e, int j, bool in,
@@ -946,6 +972,7 @@ __device__ __forceinline__ void step_one(const KCfg &kc, const ctr_batch_t &b, c
                                          const float *__restrict__ next_actions, StepCarry *seen = nullptr)
 {
     constexpr bool GROUP = (MODE & 6) == 6;
+    constexpr bool HER = KIND == STEP_HER, MANY = KIND >= PERIOD, ACTOR = KIND == PERIOD_ROLLOUT;
     static_assert(!MANY || (!GROUP && !HER), "k_step_many: one env per lane, no HER");
     static_assert(!ACTOR || MANY, "k_rollout: the period kernel's step");
     // one env per lane: the finish's inputs wait out the FK in LDS (they have landed during the
@@ -959,18 +986,7 @@ __device__ __forceinline__ void step_one(const KCfg &kc, const ctr_batch_t &b, c
         s_fin_t[threadIdx.x] = r.t;
         s_fin_ep[threadIdx.x] = r.ep;
     }
-    if constexpr (!MANY) {
-        // the step's sequence word after the packed rows (the copy-engine gather pushes it after them)
-        if (o.packed && o.packed_seq && blockIdx.x == 0 && threadIdx.x == 0)
-            *reinterpret_cast<uint4 *>(o.packed + 4 * b.n) = make_uint4(o.packed_seq, 0u, 0u, 0u);
-        // fused push gather: the previous gathered step's launch has completed, so its rows are in
-        // every rank's ring (performed at system scope); publish its sequence word there, and release
-        // this rank's slot of step gather_seq + 1 - depth (its readers ran before this launch)
-        if (blockIdx.x == 0) {
-            if (o.gather_prev) gather_publish_lane(o.gather_prev, o.gather_prev_seq);
-            if (gp) gather_release_lane(gp, o.gather_seq + 1u - (uint32_t)gp->depth);
-        }
-    }
+    if constexpr (!MANY) step_publish(b, o, gp);
     StepFlags fl;
     float4 grow = make_float4(0.f, 0.f, 0.f, 0.f);   // this lane's gather row (fused push)
     if constexpr (GROUP) {
@@ -1046,7 +1062,40 @@ __device__ __forceinline__ void step_one(const KCfg &kc, const ctr_batch_t &b, c
             for (int i = 0; i < 3; ++i) seen->ag[i] = ag[i];     // (the reset's after a pooled reset)
         }
     }
-    step_epilogue(b, o, autoreset, fl, e, live, gp, slot_free0, grow, !MANY, QUEUE);
+    step_epilogue(b, o, autoreset, fl, e, live, gp, slot_free0, grow, !MANY, KIND != PERIOD_TAIL);
+}
+
+// step_one as the period kernels' loops call it, on their locals: actions = NULL (the action is in
+// r), her = NULL, j = 0, in = live, gp = NULL, slot_free0.  (A macro: as a function, one more level
+// of inlining with an optimisation round of its own, it changed all the code of every k_step_many.)
+#define PERIOD_STEP(KIND, NEXT_ACTIONS, SEEN)                                                          \
+    step_one<MODE, KIND>(kc, b, nullptr, o, autoreset, nullptr, s_sys, s_raw, e, 0, live, live, r, nullptr, true,    \
+                         NEXT_ACTIONS, SEEN)
+
+// The prologue the period kernels share, in two halves: a kernel's own loads go between them, so
+// that their latency too hides behind the tables' (step_body).  period_load: the table inputs'
+// loads, then the row loads; ACTION: with the first step's action row, seq->a[0] (else seq is not read).
+// (e and live come from the caller: the generated code depends on what it computes between them and here.)
+template <bool ACTION = true>
+__device__ __forceinline__ void period_load(const KCfg &kc, const ctr_batch_t &b, const ctr_action_seq_t *seq,
+                                            int64_t e, bool live, StageRegs &stg, StepRows &r)
+{
+    stage_load(kc, stg);
+    __builtin_amdgcn_sched_barrier(0);       // keep the table loads ahead of the row loads
+    step_rows_load<ACTION>(b, ACTION ? seq->a[0] : nullptr, live ? e : b.n - 1, r);
+}
+
+// period_stage: the staging and its barrier.  CTR_AUTORESET_POOLED: no step of the period appends
+// to either miss counter; zero what the k steps would have zeroed one by one (the other parity's,
+// and from the second step on this one's).
+__device__ __forceinline__ void period_stage(const KCfg &kc, const ctr_batch_t &b, int32_t k, int32_t autoreset,
+                                             SysK *s_sys, ctr_tube_raw_t *s_raw, const StageRegs &stg)
+{
+    stage_systems<true>(kc, s_sys, s_raw, &stg);
+    if (autoreset == CTR_AUTORESET_POOLED && blockIdx.x == 0 && threadIdx.x == 0) {
+        b.work[(b.work_parity & 1) ^ 1] = 0;
+        if (k > 1) b.work[b.work_parity & 1] = 0;
+    }
 }
 
 // k_step / k_step_her: the staging, then one step.
@@ -1077,8 +1126,8 @@ __device__ __forceinline__ void step_body(const KCfg &kc, const ctr_batch_t &b, 
     const uint32_t rel0 = gp ? gather_release_load(gp, o.gather_seq) : 0u;
     stage_systems<!GROUP>(kc, s_sys, s_raw, &stg);
     const bool slot_free0 = gp ? gather_slot_free(gp, o.gather_seq, rel0) : true;
-    step_one<MODE, HER, false>(kc, b, actions, o, autoreset, her, s_sys, s_raw, e, j, in, live, r, gp, slot_free0,
-                               nullptr);
+    step_one<MODE, HER ? STEP_HER : STEP>(kc, b, actions, o, autoreset, her, s_sys, s_raw, e, j, in, live, r, gp,
+                                          slot_free0, nullptr);
 }
 
 // k_step_many: the staging once, then the k steps of the period, each wave on its own 64 envs
@@ -1094,23 +1143,11 @@ __device__ __forceinline__ void step_body_many(const KCfg &kc, const ctr_batch_t
     const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     const bool live = e < b.n;
     StageRegs stg;
-    stage_load(kc, stg);
-    __builtin_amdgcn_sched_barrier(0);       // keep the table loads ahead of the row loads
     StepRows r;
-    step_rows_load(b, seq.a[0], live ? e : b.n - 1, r);
-    stage_systems<true>(kc, s_sys, s_raw, &stg);
-    // CTR_AUTORESET_POOLED: no step of the period appends to either miss counter; zero what the k
-    // steps would have zeroed one by one (the other parity's, and from the second step on this one's)
-    if (autoreset == CTR_AUTORESET_POOLED && blockIdx.x == 0 && threadIdx.x == 0) {
-        b.work[(b.work_parity & 1) ^ 1] = 0;
-        if (k > 1) b.work[b.work_parity & 1] = 0;
-    }
+    period_load(kc, b, &seq, e, live, stg, r);
+    period_stage(kc, b, k, autoreset, s_sys, s_raw, stg);
     #pragma unroll 1
-    for (int32_t i = 0; i < k; ++i) {
-        const float *nxt = i + 1 < k ? seq.a[i + 1] : nullptr;
-        step_one<MODE, false, true>(kc, b, nullptr, o, autoreset, nullptr, s_sys, s_raw, e, 0, live, live, r, nullptr,
-                                    true, nxt);
-    }
+    for (int32_t i = 0; i < k; ++i) PERIOD_STEP(PERIOD, i + 1 < k ? seq.a[i + 1] : nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1174,12 +1211,7 @@ __device__ __forceinline__ void step_body_pair(const KCfg &kc, const ctr_batch_t
     if (threadIdx.x < 256) s_hist[threadIdx.x] = 0;
     stage_systems(kc, s_sys, s_raw);         // (its barrier also orders the histogram's zeroing)
     const bool slot_free0 = gp ? gather_slot_free(gp, o.gather_seq, rel0) : true;
-    if (o.packed && o.packed_seq && blockIdx.x == 0 && threadIdx.x == 0)
-        *reinterpret_cast<uint4 *>(o.packed + 4 * b.n) = make_uint4(o.packed_seq, 0u, 0u, 0u);
-    if (blockIdx.x == 0) {
-        if (o.gather_prev) gather_publish_lane(o.gather_prev, o.gather_prev_seq);
-        if (gp) gather_release_lane(gp, o.gather_seq + 1u - (uint32_t)gp->depth);
-    }
+    step_publish(b, o, gp);
     const int sn = clamp_sys(s_in, kc.c.n_systems);
     set_action_substeps(s_sys[sn], kc.c.constrain_alpha != 0, kc.c.n_substeps, q, a_in);
     // rank by predicted work (a counting sort over 256 buckets, heaviest first, dead envs last):
@@ -2039,6 +2071,47 @@ inline int64_t reset_lanes(const KCfg &kc) { return (kc.mode & 6) == 6 ? 2 * SEG
         }                                                                                          \
     } while (0)
 
+// a launch with more than 64 KB of dynamic LDS says so first (per device and kernel: a host call
+// of about a microsecond, not worth a table of what has been said where)
+template <typename K>
+int allow_dynamic_lds(K kernel, size_t bytes)
+{
+    if (bytes <= 64 * 1024) return 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)bytes) != hipSuccess)
+        return hip_check("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+    return 0;
+}
+
+// One case of CTR_LAUNCH_PERIOD's switch: launch K<M> (returns on an error).
+#define CTR_PERIOD_CASE(K, M, GRID, SHM, STREAM, ...)                                                \
+    if (int r_ = allow_dynamic_lds(K<M>, SHM)) return r_;                                          \
+    hipLaunchKernelGGL(K<M>, GRID, dim3(BLOCK), SHM, STREAM, __VA_ARGS__);                           \
+    break;
+// Launch period kernel template K<MODE> for the runtime mode: the one-env-per-lane modes but 1
+// (period_refuse_mode1; mode 2 in a build without the lane pairs).  CASE1: empty, or k_step_many's
+// `case 1:`, at its place in the order in which the kernels are named (step_launch).
+#define CTR_LAUNCH_PERIOD(K, MODE, CASE1, GRID, SHM, STREAM, ...)                                    \
+    do {                                                                                           \
+        switch (MODE) {                                                                            \
+        case 0: CTR_PERIOD_CASE(K, 0, GRID, SHM, STREAM, __VA_ARGS__)                               \
+        CASE1                                                                                      \
+        case 2: CTR_PERIOD_CASE(K, 2, GRID, SHM, STREAM, __VA_ARGS__)                               \
+        case 3: CTR_PERIOD_CASE(K, 3, GRID, SHM, STREAM, __VA_ARGS__)                               \
+        case 4: CTR_PERIOD_CASE(K, 4, GRID, SHM, STREAM, __VA_ARGS__)                               \
+        default: CTR_PERIOD_CASE(K, 5, GRID, SHM, STREAM, __VA_ARGS__)                              \
+        }                                                                                          \
+    } while (0)
+
+// (mode 1: k_step_many already fills the register file; a period kernel that does more would spill)
+int period_refuse_mode1(const KCfg &kc, const char *who, const char *instead)
+{
+    if (kc.mode != 1) return 0;
+    snprintf(g_err, sizeof g_err, "%s: not for the compliant model's scipy RK45 with y pre-curvature (the kernel would "
+             "spill to scratch); use %s", who, instead);
+    return CTR_EINVAL;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2183,16 +2256,17 @@ int ctr_step(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const float 
     return step_launch(cfg, batch, actions, out, autoreset, nullptr, stream);
 }
 
-// ctr_step_many's checks, all before any HIP call (ctr_step_period repeats them); on success
-// *kc_out, *seq_out hold the kernel arguments.
+// ctr_step_many's checks, all before any HIP call (ctr_step_period and ctr_rollout repeat them,
+// with its messages); on success *kc_out, *seq_out hold the kernel arguments.  seq_out == NULL:
+// the caller has no action table (ctr_rollout), and actions is not looked at.
 static int step_many_check(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_action_seq_t *actions,
                            int32_t k, const ctr_step_out_t *out, int32_t autoreset, KCfg *kc_out,
                            ctr_action_seq_t *seq_out)
 {
     if (int r = check_cfg(cfg)) return r;
-    if (!batch || !out || !actions) return fail(CTR_EINVAL, "ctr_step_many: NULL argument");
+    if (!batch || !out || (seq_out && !actions)) return fail(CTR_EINVAL, "ctr_step_many: NULL argument");
     if (k < 1 || k > CTR_STEP_MANY_MAX) return fail(CTR_EINVAL, "ctr_step_many: k must be in 1..CTR_STEP_MANY_MAX (64)");
-    for (int32_t i = 0; i < k; ++i)
+    for (int32_t i = 0; seq_out && i < k; ++i)
         if (!actions->a[i]) return fail(CTR_EINVAL, "ctr_step_many: NULL action buffer among a[0..k-1]");
     const ctr_batch_t b = *batch;
     const ctr_step_out_t o = *out;
@@ -2214,7 +2288,7 @@ static int step_many_check(const ctr_env_config_t *cfg, const ctr_batch_t *batch
         return fail(CTR_EINVAL, "ctr_step_many: CTR_AUTORESET_POOLED needs a reset pool");
     if (b.pool_depth > 0 && !cfg->resample_joints) return fail(CTR_EINVAL, "the reset pool needs resample_joints");
     *kc_out = kc;
-    for (int32_t i = 0; i < CTR_STEP_MANY_MAX; ++i) seq_out->a[i] = i < k ? actions->a[i] : nullptr;
+    for (int32_t i = 0; seq_out && i < CTR_STEP_MANY_MAX; ++i) seq_out->a[i] = i < k ? actions->a[i] : nullptr;
     return 0;
 }
 
@@ -2227,17 +2301,11 @@ int ctr_step_many(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const c
     const ctr_batch_t b = *batch;
     const ctr_step_out_t o = *out;
     if (b.n == 0) return 0;
-    const dim3 g(grid_for(b.n)), blk(BLOCK);
+    const dim3 g(grid_for(b.n));
     const size_t shm = lane_lds_bytes(kc);
     hipStream_t s = (hipStream_t)stream;
-    switch (kc.mode) {
-    case 0: hipLaunchKernelGGL(k_step_many<0>, g, blk, shm, s, kc, b, seq, k, o, autoreset); break;
-    case 1: hipLaunchKernelGGL(k_step_many<1>, g, blk, shm, s, kc, b, seq, k, o, autoreset); break;
-    case 2: hipLaunchKernelGGL(k_step_many<2>, g, blk, shm, s, kc, b, seq, k, o, autoreset); break;
-    case 3: hipLaunchKernelGGL(k_step_many<3>, g, blk, shm, s, kc, b, seq, k, o, autoreset); break;
-    case 4: hipLaunchKernelGGL(k_step_many<4>, g, blk, shm, s, kc, b, seq, k, o, autoreset); break;
-    default: hipLaunchKernelGGL(k_step_many<5>, g, blk, shm, s, kc, b, seq, k, o, autoreset); break;
-    }
+    CTR_LAUNCH_PERIOD(k_step_many, kc.mode, case 1: CTR_PERIOD_CASE(k_step_many, 1, g, shm, s, kc, b, seq, k, o, autoreset),
+                      g, shm, s, kc, b, seq, k, o, autoreset);
     return hip_check("ctr_step_many launch");
 }
 
@@ -2506,10 +2574,8 @@ __device__ __forceinline__ void step_body_tail(const KCfg &kc, const ctr_batch_t
     const bool live = e < b.n;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     StageRegs stg;
-    stage_load(kc, stg);
-    __builtin_amdgcn_sched_barrier(0);       // keep the table loads ahead of the row loads
     StepRows r;
-    step_rows_load(b, seq.a[0], live ? e : b.n - 1, r);
+    period_load(kc, b, &seq, e, live, stg, r);
     // the lists as ctr_pool_refill's grid lays them out (k_refill)
     CarryHdr *ch = static_cast<CarryHdr *>(b.carry);
     const int G = refill_grid(b.n, 2);
@@ -2523,11 +2589,7 @@ __device__ __forceinline__ void step_body_tail(const KCfg &kc, const ctr_batch_t
         cnt_a = ch->count[0][threadIdx.x];
         cnt_b = ch->count[1][threadIdx.x];
     }
-    stage_systems<true>(kc, s_sys, s_raw, &stg);
-    if (autoreset == CTR_AUTORESET_POOLED && blockIdx.x == 0 && threadIdx.x == 0) {   // as k_step_many
-        b.work[(b.work_parity & 1) ^ 1] = 0;
-        if (k > 1) b.work[b.work_parity & 1] = 0;
-    }
+    period_stage(kc, b, k, autoreset, s_sys, s_raw, stg);
     if (threadIdx.x < 64) {                               // wave 0: prefix sums of the counts read
         int32_t incl = (int32_t)min((int64_t)(par_l ? cnt_b : cnt_a), sub_cap);
         #pragma unroll
@@ -2545,11 +2607,7 @@ __device__ __forceinline__ void step_body_tail(const KCfg &kc, const ctr_batch_t
     s_ep0[threadIdx.x] = r.ep;
     __syncthreads();
     #pragma unroll 1
-    for (int32_t i = 0; i < k; ++i) {
-        const float *nxt = i + 1 < k ? seq.a[i + 1] : nullptr;
-        step_one<MODE, false, true, false>(kc, b, nullptr, o, autoreset, nullptr, s_sys, s_raw, e, 0, live, live, r,
-                                           nullptr, true, nxt);
-    }
+    for (int32_t i = 0; i < k; ++i) PERIOD_STEP(PERIOD_TAIL, i + 1 < k ? seq.a[i + 1] : nullptr, nullptr);
     // ---- the refill.  Nothing below waits for another wave.
     const int par = s_par;
     const int32_t c = carry_on ? s_carried : 0;
@@ -2676,32 +2734,16 @@ int ctr_step_period(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const
     const ctr_batch_t b = *batch;
     const ctr_step_out_t o = *out;
     if (b.n == 0) return 0;
-    if (kc.mode == 1)
-        return fail(CTR_EINVAL, "ctr_step_period: not for the compliant model's scipy RK45 with y pre-curvature (the "
-                                "kernel would spill to scratch); use ctr_step_many and ctr_pool_refill");
-    const dim3 g(grid_for(b.n)), blk(BLOCK);
+    if (int r = period_refuse_mode1(kc, "ctr_step_period", "ctr_step_many and ctr_pool_refill")) return r;
     const size_t shm = lane_lds_bytes(kc);
     hipStream_t s = (hipStream_t)stream;
     const int32_t ar = CTR_AUTORESET_POOLED;
-    switch (kc.mode) {
-    case 0: hipLaunchKernelGGL(k_step_tail<0>, g, blk, shm, s, kc, b, seq, k, o, ar); break;
-    case 2: hipLaunchKernelGGL(k_step_tail<2>, g, blk, shm, s, kc, b, seq, k, o, ar); break;   // (a build without the lane pairs)
-    case 3: hipLaunchKernelGGL(k_step_tail<3>, g, blk, shm, s, kc, b, seq, k, o, ar); break;
-    case 4: hipLaunchKernelGGL(k_step_tail<4>, g, blk, shm, s, kc, b, seq, k, o, ar); break;
-    default: hipLaunchKernelGGL(k_step_tail<5>, g, blk, shm, s, kc, b, seq, k, o, ar); break;
-    }
+    CTR_LAUNCH_PERIOD(k_step_tail, kc.mode, , dim3(grid_for(b.n)), shm, s, kc, b, seq, k, o, ar);
     if (int r = hip_check("ctr_step_period launch")) return r;
     // without the lists every reset has finished in the kernel: nothing to close
     const int G = refill_grid(b.n, 2);
     if (b.carry == nullptr || b.carry_cap < (G < CARRY_SUBS ? G : CARRY_SUBS)) return 0;
-    const dim3 gc((unsigned)G);
-    switch (kc.mode) {
-    case 0: hipLaunchKernelGGL(k_tail_close<0>, gc, blk, shm, s, kc, b); break;
-    case 2: hipLaunchKernelGGL(k_tail_close<2>, gc, blk, shm, s, kc, b); break;
-    case 3: hipLaunchKernelGGL(k_tail_close<3>, gc, blk, shm, s, kc, b); break;
-    case 4: hipLaunchKernelGGL(k_tail_close<4>, gc, blk, shm, s, kc, b); break;
-    default: hipLaunchKernelGGL(k_tail_close<5>, gc, blk, shm, s, kc, b); break;
-    }
+    CTR_LAUNCH_PERIOD(k_tail_close, kc.mode, , dim3((unsigned)G), shm, s, kc, b);
     return hip_check("ctr_step_period close launch");
 }
 
@@ -2749,18 +2791,10 @@ __device__ __forceinline__ void step_body_rollout(const KCfg &kc, const ctr_batc
     const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     const bool live = e < b.n;
     const int64_t ec = live ? e : b.n - 1;
-    const bool multi = kc.c.n_systems > 1;
     StageRegs stg;
-    stage_load(kc, stg);
-    __builtin_amdgcn_sched_barrier(0);       // keep the table loads ahead of the row loads
     StepRows r;
-    r.s = b.system[ec];
-    #pragma unroll
-    for (int i = 0; i < 6; ++i) { r.q[i] = b.joints[6 * ec + i]; r.a[i] = 0.f; }
-    r.t = b.t[ec];
-    r.ep = b.epoch[ec];
-    #pragma unroll
-    for (int i = 0; i < 3; ++i) r.dg[i] = b.desired_goal[3 * ec + i];
+    period_load<false>(kc, b, nullptr, e, live, stg, r);
+    const bool multi = kc.c.n_systems > 1;
     // step 0's row from memory: the observation the last call left, rounded as write_obs rounds
     float x[20];
     {
@@ -2783,11 +2817,7 @@ __device__ __forceinline__ void step_body_rollout(const KCfg &kc, const ctr_batc
     }
     char *lds = actor_lds_base(lane_lds_bytes(kc));
     actor_stage(ak, lds);
-    stage_systems<true>(kc, s_sys, s_raw, &stg);
-    if (autoreset == CTR_AUTORESET_POOLED && blockIdx.x == 0 && threadIdx.x == 0) {   // as k_step_many
-        b.work[(b.work_parity & 1) ^ 1] = 0;
-        if (k > 1) b.work[b.work_parity & 1] = 0;
-    }
+    period_stage(kc, b, k, autoreset, s_sys, s_raw, stg);
     #pragma unroll 1
     for (int32_t i = 0; i < k; ++i) {
         float y[6];
@@ -2796,8 +2826,7 @@ __device__ __forceinline__ void step_body_rollout(const KCfg &kc, const ctr_batc
             #pragma unroll
             for (int j = 0; j < 6; ++j) aux.actions[((int64_t)i * b.n + e) * 6 + j] = r.a[j];
         StepCarry seen = {};                  // (lanes past n: a zero row from the second step on)
-        step_one<MODE, false, true, true, true>(kc, b, nullptr, o, autoreset, nullptr, s_sys, s_raw, e, 0, live, live, r,
-                                                nullptr, true, nullptr, &seen);
+        PERIOD_STEP(PERIOD_ROLLOUT, nullptr, &seen);
         // the next step's row from the registers the step left, rounded as write_obs rounds (every
         // lane: the row is not carried across the step)
         {
@@ -2836,18 +2865,6 @@ __global__ __launch_bounds__(BLOCK) void k_rollout(KCfg kc, ctr_batch_t b, Actor
 constexpr size_t LDS_PER_WORKGROUP = 160 * 1024;
 constexpr size_t ROLLOUT_STATIC_LDS[6] = {78976, 0, 0, 90240, 78976, 78976};
 
-// a launch with more than 64 KB of dynamic LDS says so first (per device and kernel: a host call
-// of about a microsecond, not worth a table of what has been said where)
-template <typename K>
-int allow_dynamic_lds(K kernel, size_t bytes)
-{
-    if (bytes <= 64 * 1024) return 0;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)bytes) != hipSuccess)
-        return hip_check("hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -2885,11 +2902,9 @@ int ctr_rollout(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr
     if (int r = actor_check(actor, &ak)) return r;
     if (ak.in_dim != (cfg->n_systems > 1 ? 14 : 13) + 6)
         return fail(CTR_EINVAL, "ctr_rollout: actor->in_dim must be obs_dim + 6 (19 for one system, 20 for several)");
-    // ctr_step_many's eligibility, with its messages (its action table: k placeholders, never read)
+    // ctr_step_many's eligibility, with its messages (no action table)
     KCfg kc;
-    ctr_action_seq_t seq, unused;
-    for (int32_t i = 0; i < CTR_STEP_MANY_MAX; ++i) seq.a[i] = reinterpret_cast<const float *>(sizeof(float));
-    if (int r = step_many_check(cfg, batch, &seq, k, out, autoreset, &kc, &unused)) return r;
+    if (int r = step_many_check(cfg, batch, nullptr, k, out, autoreset, &kc, nullptr)) return r;
     const ctr_rollout_aux_t ax = aux ? *aux : ctr_rollout_aux_t{};
     if ((ax.episodes || ax.successes || ax.error_sum || ax.length_sum) && autoreset != CTR_AUTORESET_POOLED)
         return fail(CTR_EINVAL, "ctr_rollout: the episode statistics need CTR_AUTORESET_POOLED (without auto-reset a done "
@@ -2897,9 +2912,7 @@ int ctr_rollout(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr
     const ctr_batch_t b = *batch;
     const ctr_step_out_t o = *out;
     if (b.n == 0) return 0;
-    if (kc.mode == 1)
-        return fail(CTR_EINVAL, "ctr_rollout: not for the compliant model's scipy RK45 with y pre-curvature (the kernel "
-                                "would spill to scratch); use ctr_actor + ctr_step");
+    if (int r = period_refuse_mode1(kc, "ctr_rollout", "ctr_actor + ctr_step")) return r;
     const size_t lane = lane_lds_bytes(kc), fixed = ROLLOUT_STATIC_LDS[kc.mode < 6 ? kc.mode : 0];
     const size_t shm = lane + ak.bytes + ACTOR_LDS_SLACK;
     if (fixed + shm > LDS_PER_WORKGROUP) {
@@ -2908,22 +2921,7 @@ int ctr_rollout(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr
                  ak.bytes, fixed, lane, LDS_PER_WORKGROUP);
         return CTR_EINVAL;
     }
-    const dim3 g(grid_for(b.n)), blk(BLOCK);
-    hipStream_t s = (hipStream_t)stream;
-#define CTR_ROLLOUT_CASE(M)                                                                           \
-    case M:                                                                                           \
-        if (int r = allow_dynamic_lds(k_rollout<M>, shm)) return r;                          \
-        hipLaunchKernelGGL(k_rollout<M>, g, blk, shm, s, kc, b, ak, k, o, autoreset, ax);             \
-        break;
-    switch (kc.mode) {
-    CTR_ROLLOUT_CASE(0)
-    CTR_ROLLOUT_CASE(2)      // (a build without the lane pairs)
-    CTR_ROLLOUT_CASE(3)
-    CTR_ROLLOUT_CASE(4)
-    default:
-    CTR_ROLLOUT_CASE(5)
-    }
-#undef CTR_ROLLOUT_CASE
+    CTR_LAUNCH_PERIOD(k_rollout, kc.mode, , dim3(grid_for(b.n)), shm, (hipStream_t)stream, kc, b, ak, k, o, autoreset, ax);
     return hip_check("ctr_rollout launch");
 }
 
