@@ -380,7 +380,6 @@ class CtrReachVecEnv(object):
             actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
         if actions.shape != (self.num_envs, 6):
             raise ValueError("actions must be [%d, 6]" % self.num_envs)
-        self.cfg.tol = float(self.goal_tolerance.get_tol())
         self._last_actions = actions
         self.step_raw(actions, stream)
         info = {"is_success": self.success.bool(), "error": self.error,
@@ -389,7 +388,10 @@ class CtrReachVecEnv(object):
         return self._obs_dict(), self.reward, self.done.bool(), info
 
     def step_raw(self, actions, stream=None):
-        """step() without building Python return values (benchmark / graph capture)."""
+        """step() without building Python return values (benchmark / graph capture).  Like every
+        method that launches a step, it judges the step with the goal-tolerance schedule's
+        current value (``update_goal_tolerance``), read when it is called."""
+        self.cfg.tol = float(self.goal_tolerance.get_tol())
         sp = _abi.stream_ptr(stream, self.device.index)
         her = self._her
         pb = self.packed_bufs
@@ -475,11 +477,14 @@ class CtrReachVecEnv(object):
         lane-pair and 8-lane group modes, auto-reset without a full pool.
         A chunk that is a whole refill period (it starts right after a refill and ends where the
         next one falls due) runs with ``tail_refill`` as one ctr_step_period launch, its refill in
-        the step kernel's tail and no ctr_pool_refill launch; the results are the same bits."""
+        the step kernel's tail and no ctr_pool_refill launch; the results are the same bits.
+        Every step of the call is judged with the goal tolerance the schedule holds when step_many
+        is called, as the step_raw calls would (no update can fall between them)."""
         torch = _torch()
         why = self.step_many_ineligible()
         if why:
             raise RuntimeError("step_many: " + why)
+        self.cfg.tol = float(self.goal_tolerance.get_tol())
         actions = list(actions)
         for a in actions:
             if (a.dtype != torch.float32 or a.device != self.device or not a.is_contiguous()

@@ -153,6 +153,29 @@ def test_two_step_periods(cuda):
     assert carried > 0
 
 
+def test_a_default_period_of_64_steps_with_its_refill_is_one_launch(cuda):
+    """The constructor's own refill_interval and pool_depth (64 / 64: no budget, no lists): a period
+    is CTR_STEP_MANY_MAX steps and a dozen resets of every env, then the refill of all of them."""
+    from ctr_reach_amd import CtrReachVecEnv, _abi
+    mk = lambda tail: CtrReachVecEnv(65, device=cuda, seed=7, max_steps_per_episode=5,  # noqa: E731
+                                     select_systems=[0, 1, 2, 3], tail_refill=tail)
+    a, b = mk(False), mk(True)
+    for e in (a, b):
+        assert e.refill_interval == 64 == _abi.CTR_STEP_MANY_MAX and e.pool_depth == 64 and e.carry is None
+        e.goal_tolerance.current_tol = 0.03
+        e.reset()
+    acts = _actions(a, cuda, 128)
+    for p in range(2):
+        epoch = b.epoch.clone()
+        a.step_many(acts[64 * p:64 * (p + 1)])
+        b.step_many(acts[64 * p:64 * (p + 1)])
+        _same(a, b, p)
+        assert int((b.epoch - epoch).min().item()) >= 12
+    assert b.tail_launches == 2 and a.tail_launches == 0
+    assert a.refills == b.refills and a.fused_launches == b.fused_launches == 2
+    assert int(b.epoch.max().item()) > 1 + 128 // 5          # more resets than the time limit gives: goals were reached
+
+
 def test_tail_refill_matches_synchronous_resets(cuda):
     """The n = 65 trajectory equals resets computed at the step that needs them (no pool)."""
     import torch

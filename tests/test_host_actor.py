@@ -84,6 +84,11 @@ def test_actor_lds_budget_and_blob_sizes():
     assert _abi.CTR_ACTOR_MAX_BYTES == 98304
     assert lib.ctr_actor_blob_bytes(_actor((128, 128, 128))) == 81920 + 1664
     assert lib.ctr_actor_blob_bytes(_actor((32,))) == 2048 + 2048 + 256
+    # the wide shapes of tests/test_gpu_actor.py (weights + biases); [224, 160] is 384 B under the budget
+    for hidden, weights, biases, nbytes in (((256,), 32768, 1152, 33920), ((256, 128), 90112, 1664, 91776),
+                                            ((224, 160), 96256, 1664, 97920), ((160, 192, 32), 86016, 1664, 87680),
+                                            ((32, 256, 32), 36864, 1408, 38272)):
+        assert lib.ctr_actor_blob_bytes(_actor(hidden)) == nbytes == weights + biases, hidden
     _shape_refuse(_actor((256, 256)), b"CTR_ACTOR_MAX_BYTES")
     assert lib.ctr_actor_blob_bytes(_actor((256, 256))) == -1
     msg = lib.ctr_last_error()
@@ -186,7 +191,8 @@ def _unpack(a, blob, hidden, in_dim):
     return out
 
 
-@pytest.mark.parametrize("hidden,in_dim", [((32,), 19), ((64, 96), 20), ((128, 128, 128), 20)])
+@pytest.mark.parametrize("hidden,in_dim", [((32,), 19), ((64, 96), 20), ((128, 128, 128), 20),
+                                           ((256, 128), 20), ((224, 160), 19), ((32, 256, 32), 20)])
 def test_pack_round_trip(hidden, in_dim):
     """Asymmetric, bf16-exact weights (W[i][j] = (1 + i + 100 j) / 256 has at most 8 significant
     bits below 2^15): the unpacked blob is bf16(W) and b, exactly."""
@@ -266,13 +272,15 @@ def _box_rows(rng, n):
     return rng.uniform(lo, hi, (n, 20)).astype(np.float32)
 
 
-@pytest.mark.parametrize("hidden", [(32,), (64, 96), (128, 128, 128)])
+@pytest.mark.parametrize("hidden", [(32,), (64, 96), (128, 128, 128), (256, 128), (224, 160), (32, 256, 32)])
 def test_emulate_is_close_to_the_float64_mlp(hidden):
     """emulate (bf16 weights and activations, split input) against the plain float64 MLP on
     U(+-1/sqrt(fan_in)) weights and rows from the observation box: max |actions / scale| difference
-    measured 1.51e-3 ([32]), 1.21e-3 ([64, 96]), 4.71e-4 ([128, 128, 128]) over 2000 rows (seed 11);
-    asserted with 2x headroom.  A property of bf16, pinned against a typo in the emulation."""
-    measured = {(32,): 1.51e-3, (64, 96): 1.21e-3, (128, 128, 128): 4.71e-4}[hidden]
+    measured 1.51e-3 ([32]), 1.21e-3 ([64, 96]), 4.71e-4 ([128, 128, 128]), 1.09e-3 ([256, 128]),
+    8.26e-4 ([224, 160]), 4.58e-4 ([32, 256, 32]) over 2000 rows (seed 11); asserted with 2x headroom.  A
+    property of bf16, pinned against a typo in the emulation."""
+    measured = {(32,): 1.51e-3, (64, 96): 1.21e-3, (128, 128, 128): 4.71e-4,
+                (256, 128): 1.09e-3, (224, 160): 8.26e-4, (32, 256, 32): 4.58e-4}[hidden]
     rng = np.random.default_rng(11)
     act = _uniform_actor(rng, hidden, 20)
     rows = _box_rows(rng, 2000)
