@@ -47,7 +47,7 @@ def lib():
         L.oracle_philox.argtypes = [P, u64]
         L.oracle_segments.argtypes = [P, P, i64, P, P, P]
         L.oracle_jacobian.argtypes = [P, P, i64, P, ci, ci, ci, ctypes.c_double, P, P]
-        L.oracle_fk_shape.argtypes = [P, P, i64, P, ci, P, P, P, P, P]
+        L.oracle_fk_shape_ex.argtypes = [P, P, i64, P, ci, ci, P, P, P, P, P]
         L.oracle_fk_segattempts.argtypes = [P, P, i64, P, P]
         L.oracle_domain_systems.argtypes = [i64, P, P, P, P, ctypes.c_double, u64, P, i64, P]
         _lib = L
@@ -127,17 +127,18 @@ def domain_systems(n, rand, seed, epoch, env_base=0, system=None, params=None, s
     return out
 
 
-def fk_shape(joints, system=None, systems=None, cap=270):
+def fk_shape(joints, system=None, systems=None, cap=270, model="compliant"):
     """Model.forward_kinematics with Model.r (model.py:66-68, 119-174): dict tip [n, 3],
-    r [n, cap, 3] and s [n, cap] (NaN past npts), npts [n], status [n]."""
+    r [n, cap, 3] and s [n, cap] (NaN past npts), npts [n], status [n].  model="rigid": the same
+    dense output of the build's torsionally-rigid model."""
     q = np.ascontiguousarray(joints, dtype=np.float32).reshape(-1, 6)
     n = q.shape[0]
     s = None if system is None else np.ascontiguousarray(np.broadcast_to(system, (n,)), dtype=np.int32)
     systems = systems if systems is not None else make_systems()
     tip = np.zeros((n, 3)); r = np.full((n, cap, 3), np.nan); sv = np.full((n, cap), np.nan)
     npts = np.zeros(n, np.int32); status = np.zeros(n, np.int32)
-    lib().oracle_fk_shape(_p(q), _p(s), n, ctypes.cast(systems, ctypes.c_void_p), int(cap), _p(tip), _p(r), _p(sv),
-                          _p(npts), _p(status))
+    lib().oracle_fk_shape_ex(_p(q), _p(s), n, ctypes.cast(systems, ctypes.c_void_p), MODELS[model], int(cap),
+                             _p(tip), _p(r), _p(sv), _p(npts), _p(status))
     return dict(tip=tip, r=r, s=sv, npts=npts, status=status)
 
 

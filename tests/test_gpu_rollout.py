@@ -6,6 +6,8 @@ the 64-step default period and the moving goal-tolerance schedule."""
 import numpy as np
 import pytest
 
+from test_oracle_uy import uy_systems as _uy_systems
+
 pytestmark = pytest.mark.gpu
 
 KEYS = ("joints", "desired_goal", "achieved_goal", "t", "epoch", "system", "obs", "reward", "done", "success", "error",
@@ -43,16 +45,6 @@ def _same(a, b, keys, where):
     torch.cuda.synchronize()
     for k in keys:
         assert torch.equal(getattr(a, k), getattr(b, k)), (where, k)
-
-
-def _uy_systems():
-    """The registered systems with a y pre-curvature on two tubes: the kernels' MODE bit 1."""
-    from ctr_reach_amd.systems import default_systems_parameters
-    p = default_systems_parameters()
-    for name in p:
-        p[name]["tube_0"]["y_curvature"] = 3.0
-        p[name]["tube_1"]["y_curvature"] = -2.0
-    return p
 
 
 class _EagerStats(object):

@@ -10,6 +10,8 @@ tolerance in plain float64."""
 import numpy as np
 import pytest
 
+from test_oracle_uy import uy_systems as _uy_systems
+
 pytestmark = pytest.mark.gpu
 
 KEYS = ("joints", "desired_goal", "achieved_goal", "t", "epoch", "system", "obs", "reward", "done", "success", "error",
@@ -41,16 +43,6 @@ def _same(a, b, keys, where):
     torch.cuda.synchronize()
     for k in keys:
         assert torch.equal(getattr(a, k), getattr(b, k)), (where, k)
-
-
-def _uy_systems():
-    """The registered systems with a y pre-curvature on two tubes: the kernels' MODE bit 1."""
-    from ctr_reach_amd.systems import default_systems_parameters
-    p = default_systems_parameters()
-    for name in p:
-        p[name]["tube_0"]["y_curvature"] = 3.0
-        p[name]["tube_1"]["y_curvature"] = -2.0
-    return p
 
 
 # kernel modes: {} 0, rigid 4; with y pre-curvature 1, rigid 5, fixed-step RK4 on the compliant model 3

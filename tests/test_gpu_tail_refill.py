@@ -309,12 +309,8 @@ def test_the_switches_keep_the_trailing_refill(cuda, monkeypatch):
 def test_y_pre_curvature_on_the_compliant_rk45_keeps_the_refill_launch(cuda):
     """The one step_many mode ctr_step_period refuses (its kernel would need scratch): step_many
     runs it through ctr_step_many and ctr_pool_refill whatever tail_refill says."""
-    from ctr_reach_amd.systems import default_systems_parameters
-    p = default_systems_parameters()
-    for name in p:
-        p[name]["tube_0"]["y_curvature"] = 3.0
-        p[name]["tube_1"]["y_curvature"] = -2.0
-    kw = dict(ctr_systems_parameters=p)
+    from test_oracle_uy import uy_systems
+    kw = dict(ctr_systems_parameters=uy_systems())
     a, b = _env(cuda, 65, False, **kw), _env(cuda, 65, True, **kw)
     assert b.tail_refill and not b._tail_eligible()
     acts = _actions(a, cuda, 2 * R)
