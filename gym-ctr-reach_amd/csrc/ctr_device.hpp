@@ -2240,4 +2240,45 @@ __device__ __forceinline__ void domain_system(const ctr_system_t &base, const ct
     }
 }
 
+// Exploration noise on one env's six actions (include/ctr_reach_amd.h, "Exploration noise": the
+// specification): stable-baselines' clipped Gaussian action noise, or with probability random_eps
+// a uniform action of the box.  A pure function of (x.seed, env, epoch, t): two Philox blocks of
+// stream 6.  Every product and sum is spelled out (__fmul_rn, __fsub_rn, fmaf), so the kernels that
+// inline it give the same bits whatever their contraction choices.
+__device__ __forceinline__ void explore_lane(const ctr_explore_t &x, const float scale[6], uint64_t env,
+                                             uint32_t epoch, int32_t t, float a[6])
+{
+#pragma clang fp contract(off)
+    bool any = x.random_eps != 0.f;
+    #pragma unroll
+    for (int i = 0; i < 6; ++i) any = any || x.sigma[i] != 0.f;
+    if (!any) return;                                     // the no-op case: the bits stay
+    const uint32_t k0 = (uint32_t)x.seed, k1 = (uint32_t)(x.seed >> 32);
+    const uint32_t c2 = (uint32_t)env, c3 = (uint32_t)(env >> 32) ^ (6u << 24);
+    uint32_t w0[4] = {(uint32_t)t, epoch, c2, c3}, w1[4] = {(uint32_t)t | (1u << 16), epoch, c2, c3};
+    philox(w0, k0, k1);
+    philox(w1, k0, k1);
+    const float u[7] = {(float)(w0[0] >> 8) * 0x1p-24f, (float)(w0[1] >> 8) * 0x1p-24f, (float)(w0[2] >> 8) * 0x1p-24f,
+                        (float)(w0[3] >> 8) * 0x1p-24f, (float)(w1[0] >> 8) * 0x1p-24f, (float)(w1[1] >> 8) * 0x1p-24f,
+                        (float)(w1[2] >> 8) * 0x1p-24f};
+    if (u[6] < x.random_eps) {
+        #pragma unroll
+        for (int i = 0; i < 6; ++i) a[i] = __fmul_rn(scale[i], __fsub_rn(__fmul_rn(2.f, u[i]), 1.f));
+        return;
+    }
+    #pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float r = sqrtf(__fmul_rn(-2.f, logf(__fsub_rn(1.f, u[2 * j]))));
+        float sn, cs;
+        sincosf(__fmul_rn(6.2831855f, u[2 * j + 1]), &sn, &cs);
+        const float z[2] = {__fmul_rn(r, cs), __fmul_rn(r, sn)};
+        #pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int i = 2 * j + h;
+            const float box = fabsf(scale[i]);
+            a[i] = fminf(fmaxf(fmaf(__fmul_rn(x.sigma[i], box), z[h], a[i]), -box), box);
+        }
+    }
+}
+
 }  // namespace ctr

@@ -16,6 +16,9 @@
 //   k_rollout     k_step_many with each step's action computed by an MLP actor from the observation
 //                 the step before left in the lane's registers (ctr_rollout, at the end of the file)
 //   k_actor       the MLP actor alone, one row per lane, its blob staged into LDS (ctr_actor.inc)
+//   k_collect     k_rollout with exploration noise on each action and each step recorded into the HER
+//                 store (ctr_collect, at the end of the file)
+//   k_explore     the exploration noise alone, one env per lane (ctr_explore; explore_lane, ctr_device.hpp)
 //   k_ik          the damped-least-squares IK loop and a waypoint path in one launch, 7 lanes of one
 //                 wave per target (ctr_ik_dls)
 //   k_reset       CtrReachEnv.reset, TWO lanes per env (goal FK | start FK in parallel),
@@ -963,7 +966,10 @@ __device__ __forceinline__ void step_publish(const ctr_batch_t &b, const ctr_ste
 // PERIOD_TAIL (k_step_tail): a pooled reset is not appended to the refill queue.
 // PERIOD_ROLLOUT (k_rollout): r.a holds the action the actor gave for this step and there is no
 // next_actions; on return *seen holds what the actor and the statistics take from the step.
-enum StepKind { STEP, STEP_HER, PERIOD, PERIOD_TAIL, PERIOD_ROLLOUT };
+// PERIOD_COLLECT (k_collect): PERIOD_ROLLOUT that records the step into the HER store as STEP_HER
+// does; the action row waits out the FK in the (otherwise idle) next-action columns of the LDS and
+// is recorded from there, not from registers the FK would have to keep.
+enum StepKind { STEP, STEP_HER, PERIOD, PERIOD_TAIL, PERIOD_ROLLOUT, PERIOD_COLLECT };
 template <int MODE, StepKind KIND>
 __device__ __forceinline__ void step_one(const KCfg &kc, const ctr_batch_t &b, const float *__restrict__ actions,
                                          const ctr_step_out_t &o, int32_t autoreset, const ctr_her_t *her,
@@ -972,8 +978,9 @@ __device__ __forceinline__ void step_one(const KCfg &kc, const ctr_batch_t &b, c
                                          const float *__restrict__ next_actions, StepCarry *seen = nullptr)
 {
     constexpr bool GROUP = (MODE & 6) == 6;
-    constexpr bool HER = KIND == STEP_HER, MANY = KIND >= PERIOD, ACTOR = KIND == PERIOD_ROLLOUT;
-    static_assert(!MANY || (!GROUP && !HER), "k_step_many: one env per lane, no HER");
+    constexpr bool COLLECT = KIND == PERIOD_COLLECT;
+    constexpr bool HER = KIND == STEP_HER || COLLECT, MANY = KIND >= PERIOD, ACTOR = KIND >= PERIOD_ROLLOUT;
+    static_assert(!MANY || (!GROUP && (!HER || COLLECT)), "k_step_many: one env per lane; HER in k_collect only");
     static_assert(!ACTOR || MANY, "k_rollout: the period kernel's step");
     // one env per lane: the finish's inputs wait out the FK in LDS (they have landed during the
     // staging), not in registers the FK loop would have to keep
@@ -1036,7 +1043,7 @@ __device__ __forceinline__ void step_one(const KCfg &kc, const ctr_batch_t &b, c
         set_action_substeps(sy, kc.c.constrain_alpha != 0, kc.c.n_substeps, q, r.a);
         if constexpr (MANY) {
             #pragma unroll
-            for (int i = 0; i < 6; ++i) next_action_lds()[i][threadIdx.x] = a_nx[i];
+            for (int i = 0; i < 6; ++i) next_action_lds()[i][threadIdx.x] = COLLECT ? r.a[i] : a_nx[i];
         }
         FkStats st = {0, 0, 0, 0, 0};
         double ag[3];
@@ -1045,8 +1052,16 @@ __device__ __forceinline__ void step_one(const KCfg &kc, const ctr_batch_t &b, c
         #pragma unroll
         for (int i = 0; i < 3; ++i) dg_f[i] = s_fin_dg[i][threadIdx.x];
         StepCarry nx;
-        step_finish(kc, b, o, e, s, q, ag, st, autoreset, fl, her, MANY ? nullptr : actions + 6 * e, pp,
-                    s_fin_t[threadIdx.x], s_fin_ep[threadIdx.x], dg_f, grow, MANY ? &nx : nullptr);
+        if constexpr (COLLECT) {
+            float a_rec[6];                  // the step's own action, for the HER step row
+            #pragma unroll
+            for (int i = 0; i < 6; ++i) a_rec[i] = next_action_lds()[i][threadIdx.x];
+            step_finish(kc, b, o, e, s, q, ag, st, autoreset, fl, her, a_rec, pp,
+                        s_fin_t[threadIdx.x], s_fin_ep[threadIdx.x], dg_f, grow, &nx);
+        } else {
+            step_finish(kc, b, o, e, s, q, ag, st, autoreset, fl, her, MANY ? nullptr : actions + 6 * e, pp,
+                        s_fin_t[threadIdx.x], s_fin_ep[threadIdx.x], dg_f, grow, MANY ? &nx : nullptr);
+        }
         if constexpr (MANY) {
             r.s = nx.s;
             r.t = nx.t;
@@ -2781,10 +2796,34 @@ __global__ __launch_bounds__(BLOCK) void k_actor(ActorK ak, const float *__restr
     }
 }
 
-template <int MODE>
+// Kernel-argument copy of the exploration noise with the action box (ctr_explore: the caller's
+// scale; ctr_collect: the actor's); on = 0: no noise (a wave-uniform branch around it).
+struct ExploreK {
+    ctr_explore_t x;
+    float scale[6];
+    int32_t on;
+};
+
+// ctr_explore: the noise alone, one env per lane, on the batch's current clocks.
+__global__ __launch_bounds__(BLOCK) void k_explore(ExploreK xk, ctr_batch_t b, float *__restrict__ actions)
+{
+    const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (e >= b.n) return;
+    float a[6];
+    #pragma unroll
+    for (int i = 0; i < 6; ++i) a[i] = actions[6 * e + i];
+    explore_lane(xk.x, xk.scale, (uint64_t)(b.env_base + e), b.epoch[e], b.t[e], a);
+    #pragma unroll
+    for (int i = 0; i < 6; ++i) actions[6 * e + i] = a[i];
+}
+
+// k_rollout's body, and with COLLECT k_collect's: each step's action perturbed by the noise (from
+// the clocks the lane carries) and the step recorded into the HER store.
+template <int MODE, bool COLLECT = false>
 __device__ __forceinline__ void step_body_rollout(const KCfg &kc, const ctr_batch_t &b, const ActorK &ak, int32_t k,
                                                   const ctr_step_out_t &o, int32_t autoreset,
-                                                  const ctr_rollout_aux_t &aux)
+                                                  const ctr_rollout_aux_t &aux, const ExploreK &xk = ExploreK{},
+                                                  const HerK &hk = HerK{})
 {
     __shared__ SysK s_sys[CTR_MAX_SYSTEMS];
     __shared__ ctr_tube_raw_t s_raw[CTR_MAX_SYSTEMS];
@@ -2822,11 +2861,19 @@ __device__ __forceinline__ void step_body_rollout(const KCfg &kc, const ctr_batc
     for (int32_t i = 0; i < k; ++i) {
         float y[6];
         actor_wave(ak, lds, x, r.a, y);       // every lane of the wave, outside the live region
+        if constexpr (COLLECT) {
+            // the noise of (env, reset number, clock before the step): its temporaries die here
+            if (xk.on && live) explore_lane(xk.x, xk.scale, (uint64_t)(b.env_base + e), r.ep, r.t, r.a);
+        }
         if (aux.actions && live)
             #pragma unroll
             for (int j = 0; j < 6; ++j) aux.actions[((int64_t)i * b.n + e) * 6 + j] = r.a[j];
         StepCarry seen = {};                  // (lanes past n: a zero row from the second step on)
-        PERIOD_STEP(PERIOD_ROLLOUT, nullptr, &seen);
+        if constexpr (COLLECT)
+            step_one<MODE, PERIOD_COLLECT>(kc, b, nullptr, o, autoreset, &hk.h, s_sys, s_raw, e, 0, live, live, r, nullptr,
+                                           true, nullptr, &seen);
+        else
+            PERIOD_STEP(PERIOD_ROLLOUT, nullptr, &seen);
         // the next step's row from the registers the step left, rounded as write_obs rounds (every
         // lane: the row is not carried across the step)
         {
@@ -2860,10 +2907,64 @@ __global__ __launch_bounds__(BLOCK) void k_rollout(KCfg kc, ctr_batch_t b, Actor
     if constexpr (rollout_mode<MODE>()) step_body_rollout<MODE>(kc, b, ak, k, o, autoreset, aux);
 }
 
-// LDS of a workgroup on gfx950, and the static LDS of k_rollout<MODE> (the build's resource-usage
-// remarks): what the blob and the domain tables share the rest with.
+// k_rollout with the exploration noise on the actions and the HER recording in the step (ctr_collect).
+template <int MODE>
+__global__ __launch_bounds__(BLOCK) void k_collect(KCfg kc, ctr_batch_t b, ActorK ak, int32_t k, ctr_step_out_t o,
+                                                   int32_t autoreset, ctr_rollout_aux_t aux, ExploreK xk, HerK hk)
+{
+    if constexpr (rollout_mode<MODE>()) step_body_rollout<MODE, true>(kc, b, ak, k, o, autoreset, aux, xk, hk);
+}
+
+// LDS of a workgroup on gfx950, and the static LDS of k_rollout<MODE> and k_collect<MODE> (the
+// build's resource-usage remarks; k_collect adds no array of its own): what the blob and
+// the domain tables share the rest with.
 constexpr size_t LDS_PER_WORKGROUP = 160 * 1024;
 constexpr size_t ROLLOUT_STATIC_LDS[6] = {78976, 0, 0, 90240, 78976, 78976};
+
+// ctr_explore's checks of the noise and the box (ctr_collect repeats them); fills the kernel argument.
+int explore_check(const ctr_explore_t *x, const float *scale, ExploreK *xk)
+{
+    memset(xk, 0, sizeof *xk);
+    if (!x || !scale) return fail(CTR_EINVAL, "explore: NULL argument");
+    for (int i = 0; i < 6; ++i) {
+        if (!isfinite(x->sigma[i]) || x->sigma[i] < 0.f) return fail(CTR_EINVAL, "explore: sigma must be finite and >= 0");
+        if (!isfinite(scale[i])) return fail(CTR_EINVAL, "explore: scale must be finite");
+        xk->scale[i] = scale[i];
+    }
+    if (!(x->random_eps >= 0.f && x->random_eps <= 1.f)) return fail(CTR_EINVAL, "explore: random_eps must be in [0, 1]");
+    xk->x = *x;
+    xk->on = 1;
+    return 0;
+}
+
+// ctr_rollout's checks, all before any HIP call (ctr_collect repeats them, with its messages); on
+// success the kernel arguments, and *shm = the launch's dynamic LDS.
+int rollout_check(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *actor, int32_t k,
+                  const ctr_step_out_t *out, int32_t autoreset, const ctr_rollout_aux_t *aux, KCfg *kc, ActorK *ak,
+                  ctr_rollout_aux_t *ax, size_t *shm)
+{
+    if (int r = check_cfg(cfg)) return r;
+    if (int r = actor_check(actor, ak)) return r;
+    if (ak->in_dim != (cfg->n_systems > 1 ? 14 : 13) + 6)
+        return fail(CTR_EINVAL, "ctr_rollout: actor->in_dim must be obs_dim + 6 (19 for one system, 20 for several)");
+    // ctr_step_many's eligibility, with its messages (no action table)
+    if (int r = step_many_check(cfg, batch, nullptr, k, out, autoreset, kc, nullptr)) return r;
+    *ax = aux ? *aux : ctr_rollout_aux_t{};
+    if ((ax->episodes || ax->successes || ax->error_sum || ax->length_sum) && autoreset != CTR_AUTORESET_POOLED)
+        return fail(CTR_EINVAL, "ctr_rollout: the episode statistics need CTR_AUTORESET_POOLED (without auto-reset a done "
+                                "environment stays done)");
+    if (batch->n == 0) return 0;
+    if (int r = period_refuse_mode1(*kc, "ctr_rollout", "ctr_actor + ctr_step")) return r;
+    const size_t lane = lane_lds_bytes(*kc), fixed = ROLLOUT_STATIC_LDS[kc->mode < 6 ? kc->mode : 0];
+    *shm = lane + ak->bytes + ACTOR_LDS_SLACK;
+    if (fixed + *shm > LDS_PER_WORKGROUP) {
+        snprintf(g_err, sizeof g_err, "ctr_rollout: the actor's blob (%u B) + the kernel's static LDS (%zu B) + the domain "
+                 "randomisation tables (%zu B) exceed the %zu B of LDS of a workgroup; use ctr_actor + ctr_step",
+                 ak->bytes, fixed, lane, LDS_PER_WORKGROUP);
+        return CTR_EINVAL;
+    }
+    return 0;
+}
 
 }  // namespace
 
@@ -2897,32 +2998,57 @@ int ctr_actor(const ctr_actor_t *a, const float *rows, int64_t n, float *actions
 int ctr_rollout(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *actor, int32_t k,
                 const ctr_step_out_t *out, int32_t autoreset, const ctr_rollout_aux_t *aux, void *stream)
 {
-    if (int r = check_cfg(cfg)) return r;
-    ActorK ak;
-    if (int r = actor_check(actor, &ak)) return r;
-    if (ak.in_dim != (cfg->n_systems > 1 ? 14 : 13) + 6)
-        return fail(CTR_EINVAL, "ctr_rollout: actor->in_dim must be obs_dim + 6 (19 for one system, 20 for several)");
-    // ctr_step_many's eligibility, with its messages (no action table)
     KCfg kc;
-    if (int r = step_many_check(cfg, batch, nullptr, k, out, autoreset, &kc, nullptr)) return r;
-    const ctr_rollout_aux_t ax = aux ? *aux : ctr_rollout_aux_t{};
-    if ((ax.episodes || ax.successes || ax.error_sum || ax.length_sum) && autoreset != CTR_AUTORESET_POOLED)
-        return fail(CTR_EINVAL, "ctr_rollout: the episode statistics need CTR_AUTORESET_POOLED (without auto-reset a done "
-                                "environment stays done)");
+    ActorK ak;
+    ctr_rollout_aux_t ax;
+    size_t shm = 0;
+    if (int r = rollout_check(cfg, batch, actor, k, out, autoreset, aux, &kc, &ak, &ax, &shm)) return r;
     const ctr_batch_t b = *batch;
     const ctr_step_out_t o = *out;
     if (b.n == 0) return 0;
-    if (int r = period_refuse_mode1(kc, "ctr_rollout", "ctr_actor + ctr_step")) return r;
-    const size_t lane = lane_lds_bytes(kc), fixed = ROLLOUT_STATIC_LDS[kc.mode < 6 ? kc.mode : 0];
-    const size_t shm = lane + ak.bytes + ACTOR_LDS_SLACK;
-    if (fixed + shm > LDS_PER_WORKGROUP) {
-        snprintf(g_err, sizeof g_err, "ctr_rollout: the actor's blob (%u B) + the kernel's static LDS (%zu B) + the domain "
-                 "randomisation tables (%zu B) exceed the %zu B of LDS of a workgroup; use ctr_actor + ctr_step",
-                 ak.bytes, fixed, lane, LDS_PER_WORKGROUP);
-        return CTR_EINVAL;
-    }
     CTR_LAUNCH_PERIOD(k_rollout, kc.mode, , dim3(grid_for(b.n)), shm, (hipStream_t)stream, kc, b, ak, k, o, autoreset, ax);
     return hip_check("ctr_rollout launch");
+}
+
+int ctr_explore(const ctr_batch_t *batch, const ctr_explore_t *explore, const float *scale, float *actions,
+                void *stream)
+{
+    if (!batch) return fail(CTR_EINVAL, "ctr_explore: batch is NULL");
+    const ctr_batch_t b = *batch;
+    if (b.n < 0 || b.n > 0x7fffffff) return fail(CTR_EINVAL, "ctr_explore: batch size out of range");
+    ExploreK xk;
+    if (int r = explore_check(explore, scale, &xk)) return r;
+    if (b.n == 0) return 0;
+    if (!actions || !b.t || !b.epoch) return fail(CTR_EINVAL, "ctr_explore: actions, batch->t or batch->epoch is NULL");
+    hipLaunchKernelGGL(k_explore, dim3(grid_for(b.n)), dim3(BLOCK), 0, (hipStream_t)stream, xk, b, actions);
+    return hip_check("ctr_explore launch");
+}
+
+int ctr_collect(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *actor,
+                const ctr_explore_t *explore, const ctr_her_t *her, int32_t k, const ctr_step_out_t *out,
+                int32_t autoreset, const ctr_rollout_aux_t *aux, void *stream)
+{
+    KCfg kc;
+    ActorK ak;
+    ctr_rollout_aux_t ax;
+    size_t shm = 0;
+    if (int r = rollout_check(cfg, batch, actor, k, out, autoreset, aux, &kc, &ak, &ax, &shm)) return r;
+    // ctr_step_her's checks of the store, with its messages
+    if (int r = check_her(her, "ctr_step_her: her is NULL")) return r;
+    if (batch->n != her->n) return fail(CTR_EINVAL, "ctr_step_her: batch and store sizes differ");
+    if (batch->env_base != her->env_base) return fail(CTR_EINVAL, "ctr_step_her: batch and store env_base differ");
+    if (her->t_max != cfg->max_steps)
+        return fail(CTR_EINVAL, "ctr_step_her: her->t_max must equal cfg->max_steps (episodes close at the time limit)");
+    ExploreK xk = {};
+    if (explore)
+        if (int r = explore_check(explore, actor->scale, &xk)) return r;
+    const ctr_batch_t b = *batch;
+    const ctr_step_out_t o = *out;
+    if (b.n == 0) return 0;
+    const HerK hk = {*her};
+    CTR_LAUNCH_PERIOD(k_collect, kc.mode, , dim3(grid_for(b.n)), shm, (hipStream_t)stream, kc, b, ak, k, o, autoreset, ax,
+                      xk, hk);
+    return hip_check("ctr_collect launch");
 }
 
 }  // extern "C"

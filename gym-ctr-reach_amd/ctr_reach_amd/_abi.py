@@ -164,6 +164,12 @@ class CtrRolloutAux(ctypes.Structure):
     _fields_ = [("actions", _P), ("episodes", _P), ("successes", _P), ("error_sum", _P), ("length_sum", _P)]
 
 
+class CtrExplore(ctypes.Structure):
+    """ctr_explore_t: the exploration noise of ctr_explore / ctr_collect (added within ABI 17)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("sigma", ctypes.c_float * 6), ("random_eps", ctypes.c_float),
+                ("pad", ctypes.c_int32)]
+
+
 class CtrGatherPush(ctypes.Structure):
     _fields_ = [("src", _P), ("n", ctypes.c_int64), ("world", ctypes.c_int32), ("pad", ctypes.c_int32),
                 ("dst", _P * CTR_GATHER_MAX_RANKS), ("seqw", _P * CTR_GATHER_MAX_RANKS), ("ticket", _P),
@@ -216,7 +222,8 @@ EXPORTED = ("ctr_abi_version", "ctr_last_error", "ctr_fk", "ctr_set_action", "ct
             "ctr_her_open", "ctr_her_record", "ctr_her_sample", "ctr_step_her", "ctr_pool_requeue",
             "ctr_ipc_get_handle", "ctr_ipc_open", "ctr_ipc_close", "ctr_seqw_alloc", "ctr_seqw_free", "ctr_copy_list",
             "ctr_gather_wait", "ctr_gather_push", "ctr_gather_publish", "ctr_refill_carry_bytes", "ctr_step_many",
-            "ctr_ik_dls", "ctr_step_period", "ctr_actor_blob_bytes", "ctr_actor_pack", "ctr_actor", "ctr_rollout")
+            "ctr_ik_dls", "ctr_step_period", "ctr_actor_blob_bytes", "ctr_actor_pack", "ctr_actor", "ctr_rollout",
+            "ctr_explore", "ctr_collect")
 
 _lib = None
 
@@ -285,6 +292,11 @@ def load(path=None):
         L.ctr_actor.argtypes = [ctypes.POINTER(CtrActor), _P, i64, _P, _P, _P]
         L.ctr_rollout.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch), ctypes.POINTER(CtrActor), i32,
                                   ctypes.POINTER(CtrStepOut), i32, ctypes.POINTER(CtrRolloutAux), _P]
+    if hasattr(L, "ctr_collect"):                  # added within ABI 17 (an older build lacks them)
+        L.ctr_explore.argtypes = [ctypes.POINTER(CtrBatch), ctypes.POINTER(CtrExplore), _P, _P, _P]
+        L.ctr_collect.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch), ctypes.POINTER(CtrActor),
+                                  ctypes.POINTER(CtrExplore), ctypes.POINTER(CtrHer), i32, ctypes.POINTER(CtrStepOut), i32,
+                                  ctypes.POINTER(CtrRolloutAux), _P]
     if hasattr(L, "ctr_ik_dls"):                   # ABI 17
         L.ctr_ik_dls.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrIk), _P]
     if hasattr(L, "ctr_refill_carry_bytes"):       # ABI 12

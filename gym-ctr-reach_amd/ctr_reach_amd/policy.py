@@ -7,6 +7,9 @@ reference's stable-baselines DDPG ``MlpPolicy`` actor on HERGoalEnvWrapper's fla
     venv.rollout(actor, 20)                   # 20 closed-loop steps, one launch per refill period
 
 ``MlpActor.emulate`` is the CPU reference of the actor's arithmetic (numpy, no GPU, no library).
+
+``ExploreNoise`` is the exploration noise of the reference's DDPG + HER training on such an actor's
+actions (ctr_explore / ctr_collect), with its own numpy restatement.
 """
 import numpy as np
 
@@ -146,6 +149,94 @@ class MlpActor(object):
                                    _abi.stream_ptr(stream, self.device.index))
         _abi.check(rc, "ctr_actor")
         return (act, lg) if logits else act
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 in numpy: counter [..., 4] and key [..., 2] uint32 (broadcast against each other)
+    -> the block's four words [..., 4] uint32."""
+    c = np.asarray(counter, dtype=np.uint32)
+    k = np.asarray(key, dtype=np.uint32)
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape).astype(np.uint64) for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], shape).astype(np.uint64) for i in range(2))
+    m32 = np.uint64(0xFFFFFFFF)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2     # 32 x 32 -> 64 bits
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & m32, (p0 >> s32) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return np.stack((c0, c1, c2, c3), axis=-1).astype(np.uint32)
+
+
+class ExploreNoise(object):
+    """The exploration of the reference's DDPG + HER training (ctr_explore / ctr_collect,
+    include/ctr_reach_amd.h "Exploration noise"): Gaussian action noise of std ``sigma`` (a scalar
+    or 6 values, in units of the action box), clipped to the box, and with probability
+    ``random_eps`` a uniformly random action of the box instead.  The noise of a step is a pure
+    function of (seed, global env id, reset number, the env's clock before the step).
+
+        noise = ExploreNoise(0.3, random_eps=0.3, seed=1)
+        venv.step(venv.explore(venv.act(actor), noise))      # one launch each
+        venv.collect(actor, 20, noise)                       # the same 20 times, one launch per period
+
+    ``emulate`` is the numpy restatement (no GPU, no library)."""
+
+    STREAM = 6
+
+    def __init__(self, sigma, random_eps=0.0, seed=0):
+        s = np.asarray(sigma, dtype=np.float32).reshape(-1)
+        if s.shape == (1,):
+            s = np.repeat(s, 6)
+        if s.shape != (6,) or not np.isfinite(s).all() or (s < 0).any():
+            raise ValueError("sigma must be a scalar or 6 values, finite and >= 0")
+        eps = np.float32(random_eps)
+        if not 0.0 <= eps <= 1.0:
+            raise ValueError("random_eps must be in [0, 1]")
+        self.sigma, self.random_eps = np.ascontiguousarray(s), eps
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        x = self._struct = _abi.CtrExplore()
+        x.seed, x.random_eps = self.seed, float(eps)
+        for i in range(6):
+            x.sigma[i] = float(s[i])
+
+    def uniforms(self, genv, epoch, t):
+        """The step's seven uniforms [n, 7] float32 (exact: 24 bits each)."""
+        genv, epoch, t = np.broadcast_arrays(np.asarray(genv, dtype=np.uint64), np.asarray(epoch, dtype=np.uint64),
+                                             np.asarray(t, dtype=np.uint64))
+        m32 = np.uint64(0xFFFFFFFF)
+        key = np.array([self.seed & 0xFFFFFFFF, self.seed >> 32], dtype=np.uint32)
+        w = []
+        for blk in range(2):
+            ctr = np.stack(((t & m32) | np.uint64(blk << 16), epoch & m32, genv & m32,
+                            (genv >> np.uint64(32)) ^ np.uint64(self.STREAM << 24)), axis=-1).astype(np.uint32)
+            w.append(philox4x32(ctr, key))
+        w = np.concatenate(w, axis=-1)[..., :7]
+        return (w >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+
+    def emulate(self, genv, epoch, t, actions, scale):
+        """The noise of envs ``genv`` (global ids) in episode ``epoch`` at clock ``t`` on ``actions``
+        [n, 6] in the box ``scale`` (6 values): the perturbed actions [n, 6] float64.  The uniforms,
+        the random branch and the choice between the branches are float32 and exact (equal to the
+        device's bits); the Gaussian branch is plain float64 on them.  ``self.last_random`` marks
+        the rows that took the random action."""
+        a32 = np.asarray(actions, dtype=np.float32).reshape(-1, 6)
+        sc = np.asarray(scale, dtype=np.float32).reshape(6)
+        n = a32.shape[0]
+        self.last_random = np.zeros(n, dtype=bool)
+        if not self.sigma.any() and self.random_eps == 0:
+            return a32.astype(np.float64)                      # the no-op case: the bits stay
+        u = self.uniforms(np.broadcast_to(genv, (n,)), np.broadcast_to(epoch, (n,)), np.broadcast_to(t, (n,)))
+        rnd = u[:, 6] < self.random_eps
+        self.last_random = rnd
+        uniform = sc * (np.float32(2) * u[:, :6] - np.float32(1))            # float32, one rounding
+        u64 = u.astype(np.float64)
+        r = np.sqrt(-2.0 * np.log(1.0 - u64[:, 0:6:2]))
+        ang = float(np.float32(6.2831855)) * u64[:, 1:6:2]
+        z = np.stack((r * np.cos(ang), r * np.sin(ang)), axis=-1).reshape(n, 6)
+        box = np.abs(sc)
+        s = (self.sigma * box).astype(np.float64)                            # the float32 product
+        gauss = np.clip(a32.astype(np.float64) + s * z, -box.astype(np.float64), box.astype(np.float64))
+        return np.where(rnd[:, None], uniform.astype(np.float64), gauss)
 
 
 def _to_numpy(t):

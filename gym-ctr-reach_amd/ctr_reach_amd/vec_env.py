@@ -16,6 +16,7 @@ Semantics per environment follow CtrReachEnv (envs/ctr_reach_env.py:13-210):
 Random draws come from a Philox4x32-10 stream keyed by (seed, global env id, reset number),
 so results do not depend on how environments are sharded over GPUs.
 """
+import ctypes
 import os
 
 import numpy as np
@@ -281,12 +282,15 @@ class CtrReachVecEnv(object):
         self.nfev = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device) if on else None
         self._fill_structs()
 
-    def enable_her(self, slots=4, n_sampled_goal=4, goal_selection_strategy="future", seed=None):
+    def enable_her(self, slots=4, n_sampled_goal=4, goal_selection_strategy="future", seed=None, fused=True):
         """Bind a device HER replay feed (ctr_reach_amd.her.HerReplayBuffer): every later reset /
-        step records into it.  Call before reset()."""
+        step records into it.  Call before reset().  ``fused`` (the buffer's attribute of that
+        name): record inside the step kernel; False: a ctr_her_record launch after every step."""
         from .her import HerReplayBuffer
-        return HerReplayBuffer(self, slots=slots, n_sampled_goal=n_sampled_goal,
-                               goal_selection_strategy=goal_selection_strategy, seed=seed)
+        her = HerReplayBuffer(self, slots=slots, n_sampled_goal=n_sampled_goal,
+                              goal_selection_strategy=goal_selection_strategy, seed=seed)
+        her.fused = bool(fused)
+        return her
 
     def _obs_dict(self):
         return {"observation": self.obs, "achieved_goal": self.achieved_goal, "desired_goal": self.desired_goal}
@@ -446,6 +450,10 @@ class CtrReachVecEnv(object):
         """None if step_many can run this env's steps, else the reason it cannot."""
         if self._her is not None:
             return "not with the HER feed"
+        return self._period_ineligible()
+
+    def _period_ineligible(self):
+        # what keeps an env from every period kernel (step_many, rollout, collect)
         if self._push_gather is not None or self.packed_bufs is not None:
             return "not with packed outputs or the push gather"
         if self.integrator == "rk4":
@@ -564,15 +572,20 @@ class CtrReachVecEnv(object):
         refills run between them exactly as in step_many, which also says which envs are eligible
         (RuntimeError otherwise).  With auto-reset the per-env episode statistics accumulate in
         ``rollout_stats``.  Returns the applied actions [steps, N, 6] with ``record_actions``."""
-        torch = _torch()
         why = self.step_many_ineligible()
         if why:
             raise RuntimeError("rollout: " + why)
+        return self._closed_loop("rollout", actor, steps, record_actions, stream)
+
+    def _closed_loop(self, who, actor, steps, record_actions, stream, collect=False, noise=None):
+        """rollout()'s launches and host bookkeeping, and with ``collect`` collect()'s (ctr_collect in
+        place of ctr_rollout)."""
+        torch = _torch()
         if not self._tail_eligible():          # ctr_rollout refuses that mode as ctr_step_period does
-            raise RuntimeError("rollout: not for the compliant model's scipy RK45 with y pre-curvature (the kernel "
-                               "would spill to scratch); use act() and step_raw()")
+            raise RuntimeError("%s: not for the compliant model's scipy RK45 with y pre-curvature (the kernel "
+                               "would spill to scratch); use act() and step_raw()" % who)
         if actor.blob is None or actor.blob.device != self.obs.device:
-            raise ValueError("rollout: the actor must be on %s" % self.device)
+            raise ValueError("%s: the actor must be on %s" % (who, self.device))
         if actor.in_dim != self.obs_dim + 6:
             raise ValueError("the actor takes %d inputs, this env's rows have %d" % (actor.in_dim, self.obs_dim + 6))
         steps = int(steps)
@@ -594,11 +607,16 @@ class CtrReachVecEnv(object):
             if self.autoreset:                 # every step of the launch as step_raw would run it: POOLED
                 k = min(k, self._pooled_steps() - self._steps_since_refill)
                 if k < 1 or not self._pool_full:
-                    raise RuntimeError("rollout: the next step's resets are not all in the pool")
+                    raise RuntimeError("%s: the next step's resets are not all in the pool" % who)
                 mode = _abi.AUTORESET_POOLED
             aux.actions = rec[i].data_ptr() if rec is not None else None
-            rc = self.lib.ctr_rollout(self.cfg, self._batch, actor._struct, k, self._out, mode, aux, sp)
-            _abi.check(rc, "ctr_rollout")
+            if collect:
+                rc = self.lib.ctr_collect(self.cfg, self._batch, actor._struct, noise._struct if noise is not None else None,
+                                          self._her._h, k, self._out, mode, aux, sp)
+                _abi.check(rc, "ctr_collect")
+            else:
+                rc = self.lib.ctr_rollout(self.cfg, self._batch, actor._struct, k, self._out, mode, aux, sp)
+                _abi.check(rc, "ctr_rollout")
             self.fused_launches += 1
             if self.autoreset and k % 2:
                 self._batch.work_parity ^= 1
@@ -608,6 +626,48 @@ class CtrReachVecEnv(object):
                     self.refill_pool(stream)
             i += k
         return rec
+
+    # ------------------------------------------------------------------ data collection (policy.ExploreNoise)
+    def explore(self, actions, noise, stream=None):
+        """``noise`` (policy.ExploreNoise) on ``actions`` [N, 6] for the step the envs take next
+        (their current clocks and reset numbers), in the box ``action_space.high``: one ctr_explore
+        launch.  A contiguous float32 tensor on the env's device is perturbed in place (anything
+        else is converted, that is copied, first); returns the perturbed tensor, for step()."""
+        torch = _torch()
+        if actions.dtype != torch.float32 or actions.device != self.device or not actions.is_contiguous():
+            actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        if actions.shape != (self.num_envs, 6):
+            raise ValueError("actions must be [%d, 6]" % self.num_envs)
+        scale = (ctypes.c_float * 6)(*[float(v) for v in self.action_space.high])
+        rc = self.lib.ctr_explore(self._batch, noise._struct, scale, _abi.ptr(actions),
+                                  _abi.stream_ptr(stream, self.device.index))
+        _abi.check(rc, "ctr_explore")
+        return actions
+
+    def collect_ineligible(self):
+        """None if collect can run this env's steps, else the reason it cannot."""
+        her = self._her
+        if her is None:
+            return "needs the HER feed: call enable_her() first"
+        if not her.fused:
+            return "needs the HER feed recording inside the step: enable_her() with fused=True"
+        return self._period_ineligible()
+
+    def collect(self, actor, steps, noise=None, record_actions=False, stream=None):
+        """rollout() that collects training data: every step's action is perturbed by ``noise``
+        (policy.ExploreNoise, in the box ``actor.scale``; None: the policy's own actions) and every
+        transition is recorded into the HER store bound by enable_her(), each refill period's steps
+        as one launch (ctr_collect).  The state, the outputs, the HER store, the statistics and the
+        host bookkeeping afterwards are those of ``steps`` rounds of
+        ``step_raw(explore(act(actor), noise))``, bit for bit (with ``actor.scale`` equal to
+        ``action_space.high``, the box explore() uses).  Raises RuntimeError without enable_her()
+        (or with its unfused recording) and wherever rollout() would for an env without HER
+        (collect_ineligible).  Returns the applied, noisy actions [steps, N, 6] with
+        ``record_actions``."""
+        why = self.collect_ineligible()
+        if why:
+            raise RuntimeError("collect: " + why)
+        return self._closed_loop("collect", actor, steps, record_actions, stream, collect=True, noise=noise)
 
     def capture_steps(self, actions, stream=None):
         """Capture len(actions) consecutive steps (step_raw, with the pool refills that fall due)

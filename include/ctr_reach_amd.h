@@ -33,6 +33,11 @@
  *                       model.predict(obs, deterministic=True) of the stable-baselines DDPG MlpPolicy
  *                       actor in the evaluation loops of src/ (the loops behind evaluations*.csv),
  *                       ctr_rollout together with the env.step calls of those loops
+ *   ctr_explore / ctr_collect
+ *                       the data collection of the reference's training pipeline, stable-baselines
+ *                       DDPG under HER: NormalActionNoise clipped to the action box and
+ *                       random_exploration on the policy's action; ctr_collect together with the
+ *                       env.step calls and the replay wrapper's add() of that loop
  *   ctr_domain_params   Model.current_sys_parameters after randomize_parameters
  *                                                                          envs/model.py:20-28, model_utils.py:5-35
  *   ctr_her_open / ctr_her_record / ctr_her_sample
@@ -543,6 +548,60 @@ typedef struct ctr_rollout_aux_t {   /* every pointer device, or NULL */
 } ctr_rollout_aux_t;
 int ctr_rollout(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *actor, int32_t k,
                 const ctr_step_out_t *out, int32_t autoreset, const ctr_rollout_aux_t *aux, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Exploration noise and data collection (entry points added within ABI 17: no existing entry point
+ * or struct changes, so the number stays; a caller that needs them looks the symbols up).
+ *
+ * The reference trains with stable-baselines HER + DDPG: Gaussian action noise, clipped to the box
+ * (clip(action + NormalActionNoise, -1, 1) in the normalised box, rescaled), and with probability
+ * random_exploration a uniformly random action (action_space.sample()) instead of the policy's.
+ * Here an env's six actions are perturbed as a pure function of (explore->seed, the global env id
+ * genv = batch->env_base + e, the env's reset number `epoch`, its clock t before the step): not of
+ * the launch, the lane, the shard, or of how the steps are cut into launches.
+ *   draws   two Philox4x32-10 blocks blk = 0, 1 of stream 6: counter {t | blk << 16, epoch,
+ *           (uint32)genv, (uint32)(genv >> 32) ^ (6u << 24)}, key {(uint32)seed, (uint32)(seed >> 32)};
+ *           their words w0..w3 | w4..w7; u_i = (float)(w_i >> 8) * 2^-24 (exact in f32, in [0, 1));
+ *           w7 is not used
+ *   random  if u6 < random_eps (f32):  a_i = scale_i * (2 u_i - 1), i = 0..5 (2 u_i - 1 is exact, so
+ *           one f32 rounding, the product's)
+ *   else    (z_2j, z_2j+1) = sqrtf(-2 logf(1 - u_2j)) * (cosf, sinf)(2 pi u_2j+1), j = 0..2 (Box-Muller;
+ *           1 - u is exact and in (0, 1]; 2 pi u = 6.2831855f * u, one f32 product)
+ *           a_i = min(max(fmaf(sigma_i * |scale_i|, z_i, a_i), -|scale_i|), |scale_i|)
+ *           (sigma_i * |scale_i| one f32 product, then ONE fused multiply-add; all f32)
+ *   no-op   sigma all zero and random_eps zero: the actions keep their bits (nothing is computed)
+ * logf, sinf, cosf and sqrtf are the device library's f32 functions: the Gaussian branch matches a
+ * float64 restatement to their error, the random branch and the choice between the two bit for bit. */
+typedef struct ctr_explore_t {
+    uint64_t seed;              /* the noise stream's key                                       */
+    float    sigma[6];          /* finite, >= 0: the Gaussian's std in units of |scale_i|       */
+    float    random_eps;        /* in [0, 1]: probability of a uniformly random action          */
+    int32_t  pad;
+} ctr_explore_t;
+
+/* actions [n][6] f32 (device), perturbed in place with the batch's current t, epoch and env_base:
+ * what ctr_collect applies inside its kernel, as a launch of its own (for use with ctr_step*).
+ * Refused (CTR_EINVAL, before any HIP call): NULL arguments where n > 0, a non-finite or negative
+ * sigma, random_eps outside [0, 1], a non-finite scale. */
+int ctr_explore(const ctr_batch_t *batch, const ctr_explore_t *explore, const float *scale, float *actions,
+                void *stream);
+
+/* ctr_rollout that collects training data: every step's action is perturbed by `explore` (NULL: no
+ * noise, the branch is skipped wave-uniformly) with actor->scale as the box, and every transition
+ * is recorded into the HER store as ctr_step_her records it.  Afterwards the batch, the outputs,
+ * the pool, the refill queue, every buffer of the HER store, aux->actions (the applied, noisy
+ * actions) and the statistics are exactly what k rounds of
+ *     ctr_actor(actor, row, ...);  ctr_explore(batch, explore, actor->scale, actions, ...);
+ *     ctr_step_her(cfg, batch, actions, out, autoreset, her, ...)
+ * with batch->work_parity toggled after every step would have left, bit for bit.
+ * Refused (CTR_EINVAL, before any HIP call) wherever ctr_rollout is, with its messages (so also
+ * for the compliant model's scipy RK45 with a y pre-curvature, whose kernel would spill, and for
+ * the lane-pair and 8-lane group modes); where ctr_step_her is (a NULL or malformed store,
+ * her->t_max != cfg->max_steps, her->n or her->env_base different from the batch's); and where
+ * ctr_explore is. */
+int ctr_collect(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *actor,
+                const ctr_explore_t *explore, const ctr_her_t *her, int32_t k, const ctr_step_out_t *out,
+                int32_t autoreset, const ctr_rollout_aux_t *aux, void *stream);
 
 /* CtrReachEnv.reset for the environments with mask[i] != 0 (mask NULL = all).
  * goal [n][3] or NULL (sample a goal), system [n] or NULL (sample uniformly).
