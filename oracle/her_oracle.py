@@ -29,6 +29,10 @@ desired_goal]) and CtrReachEnv.compute_reward (envs/ctr_reach_env.py:160-170).  
 choice is the build's Philox draw (stream 4, keyed by seed, global env id, reset number, t, j),
 so GPU rows can be checked bit for bit; against stable-baselines itself the relabelling is
 "parity unpinned" (the library is absent and the reference holds no HER fixtures).
+
+sample_rows restates common/buffers.py ReplayBuffer.sample over that buffer (one uniform row index
+per sampled row, the build's Philox stream 5) directly on a copy of the device store, and
+scan_reference states what the device sampler's scratch must hold afterwards.
 """
 import numpy as np
 
@@ -80,6 +84,95 @@ def store_episode(transitions, k, strategy, tol, seed, genv, epoch):
                              reward=float(compute_reward(no["achieved_goal"], goal, tol)), next_obs=flat(no),
                              done=0.0))
     return rows
+
+
+SCAN_TILE = 1024      # CTR_HER_SCAN_TILE (include/ctr_reach_amd.h)
+
+
+def rows_per_episode(L, k, strategy):
+    """Rows _store_episode adds for episodes of L transitions (0 for L <= 0: open or dropped)."""
+    L = np.asarray(L, dtype=np.int64)
+    return np.where(L > 0, L + k * (L - 1) if strategy == "future" else L * (1 + k), 0)
+
+
+def scan_reference(length, k, strategy, tile=SCAN_TILE):
+    """What the sampler's scratch (ctr_her_t.cdf) holds after a ctr_her_sample call on a store
+    with episode lengths ``length`` [E]: (the tile-local inclusive sums of the rows per slot [E],
+    the exclusive tile offsets [tiles], the stored-row count), int64 -- cdf is their
+    concatenation."""
+    rows = rows_per_episode(length, k, strategy)
+    E = len(rows)
+    tiles = (E + tile - 1) // tile
+    local = np.zeros(E, dtype=np.int64)
+    totals = np.zeros(tiles, dtype=np.int64)
+    for b in range(tiles):
+        seg = rows[b * tile:(b + 1) * tile]
+        local[b * tile:b * tile + len(seg)] = np.cumsum(seg, dtype=np.int64)
+        totals[b] = seg.sum()
+    offsets = np.zeros(tiles, dtype=np.int64)
+    offsets[1:] = np.cumsum(totals, dtype=np.int64)[:-1]
+    return local, offsets, np.int64(totals.sum())
+
+
+STORE_BUFFERS = ("state", "step_rows", "dg", "tol", "len", "epoch")
+
+
+def store_copy(her):
+    """The store of a ctr_reach_amd.her.HerReplayBuffer as sample_rows takes it: numpy copies of
+    its buffers (device tensors) and its parameters."""
+    store = {name: getattr(her, name).cpu().numpy().copy() for name in STORE_BUFFERS}
+    store.update(n=her.venv.num_envs, slots=her.slots, t_max=her.t_max, k=her.n_sampled_goal, strategy=her.strategy,
+                 obs_dim=her.obs_dim, env_base=her.venv.env_base, seed=her.seed)
+    return store
+
+
+def sample_rows(store, B, seed, counter):
+    """ReplayBuffer.sample(B) over the rows _store_episode would have added for every stored
+    episode, slot after slot: dict of index [B, 3] int32 = (slot, t, j) and obs [B, d], action
+    [B, 6], reward [B], next_obs [B, d], done [B] float32 (d = obs_dim + 6).
+
+    ``store``: numpy copies of the episode store -- state [slots, t_max + 1, n, 24] and step_rows
+    [slots, t_max, n, 8] float32, dg [E, 3] and tol [E] float64, len and epoch [E] int32 -- and its
+    parameters n, slots, t_max, k, strategy, obs_dim, env_base, seed.  Row i is the build's Philox
+    draw (stream 5, keyed by ``seed``, ``counter``, i) over the stored rows; the sampler's own
+    prefix sums (cdf) are never read.  Nothing stored: index (-1, 0, 0) and zero rows."""
+    n, slots, k, strategy, obs_dim = store["n"], store["slots"], store["k"], store["strategy"], store["obs_dim"]
+    state, step = store["state"], store["step_rows"]
+    assert state.shape == (slots, store["t_max"] + 1, n, 24) and step.shape == (slots, store["t_max"], n, 8)
+    ag = state.view(np.float64)[..., 8:11]               # floats 16 .. 21 of a state row
+    d = obs_dim + 6
+    out = dict(index=np.zeros((B, 3), np.int32), obs=np.zeros((B, d), np.float32),
+               action=np.zeros((B, 6), np.float32), reward=np.zeros(B, np.float32),
+               next_obs=np.zeros((B, d), np.float32), done=np.zeros(B, np.float32))
+    cum = np.cumsum(rows_per_episode(store["len"], k, strategy), dtype=np.int64)
+    stored = int(cum[-1])
+    if stored == 0:
+        out["index"][:, 0] = -1
+        return out
+    counter = int(counter)
+    for i in range(B):
+        c = oracle.philox([0, counter & 0xFFFFFFFF, i, ((counter >> 32) ^ (5 << 24)) & 0xFFFFFFFF], seed)
+        idx = min(int(u53(c[0], c[1]) * stored), stored - 1)
+        slot = int(np.searchsorted(cum, idx, side="right"))
+        r = idx - (int(cum[slot - 1]) if slot else 0)
+        t, j = divmod(r, 1 + k)
+        e, s = divmod(slot, slots)
+        L = int(store["len"][slot])
+        obs_t = dict(observation=state[s, t, e, :obs_dim], achieved_goal=ag[s, t, e], desired_goal=store["dg"][slot])
+        obs_n = dict(observation=state[s, t + 1, e, :obs_dim], achieved_goal=ag[s, t + 1, e],
+                     desired_goal=store["dg"][slot])
+        reward, done = step[s, t, e, 6], float(t == L - 1)
+        if j:
+            sel = sel_index(store["seed"], store["env_base"] + e, int(store["epoch"][slot]), t, j, L, strategy)
+            goal = ag[s, sel, e]
+            obs_t, obs_n = dict(obs_t, desired_goal=goal), dict(obs_n, desired_goal=goal)
+            reward = float(compute_reward(obs_n["achieved_goal"], goal, store["tol"][slot])) + 0.0   # -0.0 -> 0.0
+            done = 0.0
+        out["index"][i] = (slot, t, j)
+        out["obs"][i], out["next_obs"][i] = flat(obs_t), flat(obs_n)
+        out["action"][i] = step[s, t, e, :6]
+        out["reward"][i], out["done"][i] = reward, done
+    return out
 
 
 class EpisodeRecorder(object):

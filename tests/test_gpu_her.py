@@ -51,10 +51,15 @@ def _run(cuda, n=48, steps=60, t_max=12, slots=4, strategy="future", k=4, select
     return env, her, rec
 
 
-@pytest.mark.parametrize("strategy,systems,fused", [("future", (0,), True), ("final", (0, 1, 2, 3), True),
-                                                    ("episode", (0,), True), ("future", (0,), False)])
-def test_sampled_rows_match_restatement(cuda, oracle_mod, strategy, systems, fused):
-    env, her, rec = _run(cuda, strategy=strategy, select_systems=systems, fused=fused)
+# the last case: 300 envs x 4 slots = 1200 slots, two scan tiles of the sampler (the others fit in one)
+@pytest.mark.parametrize("strategy,systems,fused,n",
+                         [("future", (0,), True, 48), ("final", (0, 1, 2, 3), True, 48), ("episode", (0,), True, 48),
+                          ("future", (0,), False, 48), ("future", (0,), True, 300)],
+                         ids=["future-systems0-True", "final-systems1-True", "episode-systems2-True",
+                              "future-systems3-False", "future-systems0-True-n300"])
+def test_sampled_rows_match_restatement(cuda, oracle_mod, strategy, systems, fused, n):
+    import her_oracle as H
+    env, her, rec = _run(cuda, n=n, strategy=strategy, select_systems=systems, fused=fused)
     lens, eps = her.len.cpu().numpy(), her.epoch.cpu().numpy()
     stored = np.where(lens > 0)[0]
     assert len(stored) > 100
@@ -62,10 +67,18 @@ def test_sampled_rows_match_restatement(cuda, oracle_mod, strategy, systems, fus
         key = (s // her.slots, int(eps[s]))
         assert key in rec.lengths and rec.lengths[key] == lens[s]
     assert len(her) == int(her.rows_per_episode(lens[stored]).sum())
+    counter = her._counter
     b = her.sample(8192, return_index=True)
     idx = b["index"].cpu().numpy()
     assert (idx[:, 0] >= 0).all()
     got = {k: b[k].cpu().numpy() for k in ("obs", "action", "reward", "next_obs", "done")}
+    # the draw itself: the restatement of ReplayBuffer.sample on the store copied back predicts
+    # every (slot, t, j), so the env-fed store meets the reference the synthetic stores of
+    # test_gpu_her_sampler.py meet
+    ref = H.sample_rows(H.store_copy(her), 8192, her.seed ^ 0x5DEECE66D, counter)
+    np.testing.assert_array_equal(idx, ref["index"])
+    for k in got:
+        np.testing.assert_array_equal(got[k], ref[k], err_msg=k)
     nrel = 0
     for i, (s, t, j) in enumerate(idx):
         row = rec.stored[(s // her.slots, int(eps[s]))][(t, j)]
