@@ -19,6 +19,9 @@
 //   k_collect     k_rollout with exploration noise on each action and each step recorded into the HER
 //                 store (ctr_collect, at the end of the file)
 //   k_explore     the exploration noise alone, one env per lane (ctr_explore; explore_lane, ctr_device.hpp)
+//   k_follow      k_rollout without auto-reset in which every env's goal moves along its own waypoint list
+//                 between the steps (ctr_follow, at the end of the file)
+//   k_set_goal    a new desired goal and the three observation slots that hold it, the joints kept (ctr_set_goal)
 //   k_ik          the damped-least-squares IK loop and a waypoint path in one launch, 7 lanes of one
 //                 wave per target (ctr_ik_dls)
 //   k_reset       CtrReachEnv.reset, TWO lanes per env (goal FK | start FK in parallel),
@@ -2817,14 +2820,57 @@ __global__ __launch_bounds__(BLOCK) void k_explore(ExploreK xk, ctr_batch_t b, f
     for (int i = 0; i < 6; ++i) actions[6 * e + i] = a[i];
 }
 
+// ctr_set_goal: one env per lane, no staging (the three slots need no trig table).
+__global__ __launch_bounds__(BLOCK) void k_set_goal(ctr_batch_t b, const uint8_t *__restrict__ mask,
+                                                    const double *__restrict__ goal, void *obs, int od, int f64)
+{
+    const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (e >= b.n || (mask && !mask[e])) return;
+    #pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double g = goal[3 * e + j], d = g - b.achieved_goal[3 * e + j];
+        b.desired_goal[3 * e + j] = g;
+        if (f64) static_cast<double *>(obs)[od * e + 9 + j] = d;
+        else static_cast<float *>(obs)[od * e + 9 + j] = (float)d;
+    }
+}
+
+// k_follow: the env of row e starts waypoint c in its next step.  The goal the step starts from
+// (r.dg), and of the actor's row the observation's slots 9..11 (ob) and the goal (dg); `write`
+// (the live lanes): the desired_goal row and the observation's slots, as k_set_goal stores them.
+// ag: the env's tip in f64.  The caller has checked 0 <= c < K.
+__device__ __forceinline__ void follow_retarget(const ctr_follow_t &fw, const ctr_batch_t &b, const ctr_step_out_t &o,
+                                                bool multi, bool f64, int64_t e, bool write, int32_t c,
+                                                const double ag[3], StepRows &r, float ob[14], float dg[3])
+{
+    const int od = multi ? 14 : 13;
+    const double *wp = fw.waypoints + ((int64_t)c * b.n + e) * 3;
+    #pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double g = wp[j], d = g - ag[j];
+        r.dg[j] = g;
+        dg[j] = (float)g;
+        ob[9 + j] = (float)d;
+        if (write) {
+            b.desired_goal[3 * e + j] = g;
+            if (f64) static_cast<double *>(o.obs)[od * e + 9 + j] = d;
+            else static_cast<float *>(o.obs)[od * e + 9 + j] = (float)d;
+        }
+    }
+}
+
 // k_rollout's body, and with COLLECT k_collect's: each step's action perturbed by the noise (from
-// the clocks the lane carries) and the step recorded into the HER store.
-template <int MODE, bool COLLECT = false>
+// the clocks the lane carries) and the step recorded into the HER store.  With FOLLOW k_follow's:
+// between two steps the env's goal moves along its waypoints (fw; ctr_follow in the header).  The
+// cursor and the hold count stay in their global rows, read and written between the steps by the
+// env's own lane: no register of theirs lives across the FK, and no wave waits for another.
+template <int MODE, bool COLLECT = false, bool FOLLOW = false>
 __device__ __forceinline__ void step_body_rollout(const KCfg &kc, const ctr_batch_t &b, const ActorK &ak, int32_t k,
                                                   const ctr_step_out_t &o, int32_t autoreset,
                                                   const ctr_rollout_aux_t &aux, const ExploreK &xk = ExploreK{},
-                                                  const HerK &hk = HerK{})
+                                                  const HerK &hk = HerK{}, const ctr_follow_t &fw = ctr_follow_t{})
 {
+    static_assert(!(COLLECT && FOLLOW), "k_follow: no noise and no HER");
     __shared__ SysK s_sys[CTR_MAX_SYSTEMS];
     __shared__ ctr_tube_raw_t s_raw[CTR_MAX_SYSTEMS];
     const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -2852,6 +2898,15 @@ __device__ __forceinline__ void step_body_rollout(const KCfg &kc, const ctr_batc
         }
         #pragma unroll
         for (int i = 0; i < 3; ++i) { ag[i] = (float)b.achieved_goal[3 * ec + i]; dg[i] = (float)r.dg[i]; }
+        if constexpr (FOLLOW) {
+            // step 0 starts a waypoint: the tip as the last call left it, in f64 from the batch
+            // (lanes past n: the clamped row, and no write)
+            const int32_t c = fw.cursor[ec];
+            if ((uint32_t)c < (uint32_t)fw.K && fw.held[ec] == 0) {
+                const double agd[3] = {b.achieved_goal[3 * ec], b.achieved_goal[3 * ec + 1], b.achieved_goal[3 * ec + 2]};
+                follow_retarget(fw, b, o, multi, kc.c.obs_f64 != 0, ec, live, c, agd, r, ob, dg);
+            }
+        }
         actor_row(ob, ag, dg, multi, x);
     }
     char *lds = actor_lds_base(lane_lds_bytes(kc));
@@ -2881,6 +2936,29 @@ __device__ __forceinline__ void step_body_rollout(const KCfg &kc, const ctr_batc
             obs_to_f32(seen.obs, ob);
             #pragma unroll
             for (int j = 0; j < 3; ++j) { ag[j] = (float)seen.ag[j]; dg[j] = (float)seen.dg[j]; }
+            if constexpr (FOLLOW) {
+                // the env stays on its waypoint or leaves it (recording how); a waypoint that
+                // starts in the next step of this launch moves the goal here, where the step's tip
+                // is still in registers (after the last step: the next launch's prologue does it)
+                int32_t c = live ? fw.cursor[e] : fw.K;
+                if ((uint32_t)c < (uint32_t)fw.K) {
+                    int32_t h = fw.held[e] + 1;
+                    if (h >= fw.hold || (fw.reach && seen.success)) {
+                        const int64_t w = (int64_t)c * b.n + e;
+                        if (fw.tip)
+                            #pragma unroll
+                            for (int j = 0; j < 3; ++j) fw.tip[3 * w + j] = seen.ag[j];
+                        if (fw.err) fw.err[w] = seen.error;
+                        if (fw.steps) fw.steps[w] = h;
+                        if (fw.reached) fw.reached[w] = seen.success ? 1 : 0;
+                        fw.cursor[e] = ++c;
+                        h = 0;
+                    }
+                    fw.held[e] = h;
+                    if (h == 0 && c < fw.K && i + 1 < k)
+                        follow_retarget(fw, b, o, multi, kc.c.obs_f64 != 0, e, true, c, seen.ag, r, ob, dg);
+                }
+            }
             actor_row(ob, ag, dg, multi, x);
         }
         if (live) {
@@ -2915,9 +2993,19 @@ __global__ __launch_bounds__(BLOCK) void k_collect(KCfg kc, ctr_batch_t b, Actor
     if constexpr (rollout_mode<MODE>()) step_body_rollout<MODE, true>(kc, b, ak, k, o, autoreset, aux, xk, hk);
 }
 
-// LDS of a workgroup on gfx950, and the static LDS of k_rollout<MODE> and k_collect<MODE> (the
-// build's resource-usage remarks; k_collect adds no array of its own): what the blob and
-// the domain tables share the rest with.
+// k_rollout without auto-reset (a compile-time CTR_AUTORESET_OFF: no pool code) whose envs walk
+// their waypoint lists (ctr_follow).
+template <int MODE>
+__global__ __launch_bounds__(BLOCK) void k_follow(KCfg kc, ctr_batch_t b, ActorK ak, int32_t k, ctr_step_out_t o,
+                                                  ctr_rollout_aux_t aux, ctr_follow_t fw)
+{
+    if constexpr (rollout_mode<MODE>())
+        step_body_rollout<MODE, false, true>(kc, b, ak, k, o, CTR_AUTORESET_OFF, aux, ExploreK{}, HerK{}, fw);
+}
+
+// LDS of a workgroup on gfx950, and the static LDS of k_rollout<MODE>, k_collect<MODE> and
+// k_follow<MODE> (the build's resource-usage remarks; k_collect and k_follow add no array
+// of their own): what the blob and the domain tables share the rest with.
 constexpr size_t LDS_PER_WORKGROUP = 160 * 1024;
 constexpr size_t ROLLOUT_STATIC_LDS[6] = {78976, 0, 0, 90240, 78976, 78976};
 
@@ -3049,6 +3137,44 @@ int ctr_collect(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr
     CTR_LAUNCH_PERIOD(k_collect, kc.mode, , dim3(grid_for(b.n)), shm, (hipStream_t)stream, kc, b, ak, k, o, autoreset, ax,
                       xk, hk);
     return hip_check("ctr_collect launch");
+}
+
+int ctr_set_goal(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const uint8_t *mask, const double *goal,
+                 void *obs, void *stream)
+{
+    if (int r = check_cfg(cfg)) return r;
+    if (!batch || !goal || !obs) return fail(CTR_EINVAL, "ctr_set_goal: NULL argument");
+    const ctr_batch_t b = *batch;
+    if (int r = check_batch(b, "ctr_set_goal: batch buffer missing")) return r;
+    if (b.n == 0) return 0;
+    hipLaunchKernelGGL(k_set_goal, dim3(grid_for(b.n)), dim3(BLOCK), 0, (hipStream_t)stream, b, mask, goal, obs,
+                       cfg->n_systems > 1 ? 14 : 13, cfg->obs_f64 != 0 ? 1 : 0);
+    return hip_check("ctr_set_goal launch");
+}
+
+int ctr_follow(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *actor,
+               const ctr_follow_t *follow, int32_t k, const ctr_step_out_t *out, float *actions, void *stream)
+{
+    KCfg kc;
+    ActorK ak;
+    ctr_rollout_aux_t ax;
+    size_t shm = 0;
+    // ctr_rollout's checks, with its messages (CTR_AUTORESET_OFF, no statistics)
+    ctr_rollout_aux_t aux = {};
+    aux.actions = actions;
+    if (int r = rollout_check(cfg, batch, actor, k, out, CTR_AUTORESET_OFF, &aux, &kc, &ak, &ax, &shm)) return r;
+    if (!follow) return fail(CTR_EINVAL, "ctr_follow: follow is NULL");
+    const ctr_follow_t fw = *follow;
+    if (fw.K < 1) return fail(CTR_EINVAL, "ctr_follow: K must be >= 1");
+    if (fw.hold < 1) return fail(CTR_EINVAL, "ctr_follow: hold must be >= 1");
+    if (fw.reach != 0 && fw.reach != 1) return fail(CTR_EINVAL, "ctr_follow: reach must be 0 or 1");
+    const ctr_batch_t b = *batch;
+    const ctr_step_out_t o = *out;
+    if (b.n == 0) return 0;
+    if (!fw.waypoints || !fw.cursor || !fw.held)
+        return fail(CTR_EINVAL, "ctr_follow: waypoints, cursor or held is NULL");
+    CTR_LAUNCH_PERIOD(k_follow, kc.mode, , dim3(grid_for(b.n)), shm, (hipStream_t)stream, kc, b, ak, k, o, ax, fw);
+    return hip_check("ctr_follow launch");
 }
 
 }  // extern "C"

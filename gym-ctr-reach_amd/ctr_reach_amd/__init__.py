@@ -8,11 +8,15 @@ with the environments stepped in lockstep by hand-written HIP kernels on gfx950.
   Model            batched Model.forward_kinematics operator
   make             make('CTR-Reach-v0', **overrides)
   HerReplayBuffer  device HER replay feed (stable-baselines 2 'future' relabelling)
+  MlpActor         the policy's actor, run by hand-written kernels (rollout, collect, follow)
+  paths            line / circle / helix waypoint paths for follow() and dls_ik_path
 """
-from .vec_env import CtrReachVecEnv  # noqa: F401
+from .vec_env import CtrReachVecEnv, FollowResult  # noqa: F401
 from .env import CtrReachEnv, Model, make  # noqa: F401
 from .systems import Tube, default_kwargs, default_systems_parameters  # noqa: F401
 from .goal_tolerance import GoalTolerance  # noqa: F401
 from .ik import dls_ik_path, dls_ik_position_only  # noqa: F401
 from .her import HerReplayBuffer  # noqa: F401
 from .policy import MlpActor  # noqa: F401
+from .paths import circle_path, helix_path, line_path  # noqa: F401
+from . import paths  # noqa: F401

@@ -170,6 +170,13 @@ class CtrExplore(ctypes.Structure):
                 ("pad", ctypes.c_int32)]
 
 
+class CtrFollow(ctypes.Structure):
+    """ctr_follow_t: the waypoints, cursors and per-waypoint records of ctr_follow (added within ABI 17)."""
+    _fields_ = [("waypoints", _P), ("K", ctypes.c_int32), ("hold", ctypes.c_int32), ("reach", ctypes.c_int32),
+                ("pad", ctypes.c_int32), ("cursor", _P), ("held", _P), ("tip", _P), ("err", _P), ("steps", _P),
+                ("reached", _P)]
+
+
 class CtrGatherPush(ctypes.Structure):
     _fields_ = [("src", _P), ("n", ctypes.c_int64), ("world", ctypes.c_int32), ("pad", ctypes.c_int32),
                 ("dst", _P * CTR_GATHER_MAX_RANKS), ("seqw", _P * CTR_GATHER_MAX_RANKS), ("ticket", _P),
@@ -223,7 +230,7 @@ EXPORTED = ("ctr_abi_version", "ctr_last_error", "ctr_fk", "ctr_set_action", "ct
             "ctr_ipc_get_handle", "ctr_ipc_open", "ctr_ipc_close", "ctr_seqw_alloc", "ctr_seqw_free", "ctr_copy_list",
             "ctr_gather_wait", "ctr_gather_push", "ctr_gather_publish", "ctr_refill_carry_bytes", "ctr_step_many",
             "ctr_ik_dls", "ctr_step_period", "ctr_actor_blob_bytes", "ctr_actor_pack", "ctr_actor", "ctr_rollout",
-            "ctr_explore", "ctr_collect")
+            "ctr_explore", "ctr_collect", "ctr_set_goal", "ctr_follow")
 
 _lib = None
 
@@ -297,6 +304,10 @@ def load(path=None):
         L.ctr_collect.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch), ctypes.POINTER(CtrActor),
                                   ctypes.POINTER(CtrExplore), ctypes.POINTER(CtrHer), i32, ctypes.POINTER(CtrStepOut), i32,
                                   ctypes.POINTER(CtrRolloutAux), _P]
+    if hasattr(L, "ctr_follow"):                   # added within ABI 17 (an older build lacks them)
+        L.ctr_set_goal.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch), _P, _P, _P, _P]
+        L.ctr_follow.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch), ctypes.POINTER(CtrActor),
+                                 ctypes.POINTER(CtrFollow), i32, ctypes.POINTER(CtrStepOut), _P, _P]
     if hasattr(L, "ctr_ik_dls"):                   # ABI 17
         L.ctr_ik_dls.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrIk), _P]
     if hasattr(L, "ctr_refill_carry_bytes"):       # ABI 12

@@ -627,6 +627,142 @@ class CtrReachVecEnv(object):
             i += k
         return rec
 
+    # ------------------------------------------------------------------ waypoint following (paths)
+    def set_goal(self, goal, mask=None, stream=None):
+        """A new desired goal for all envs (or those with mask != 0), the joints kept: one
+        ctr_set_goal launch.  goal: [N, 3] (or [1, 3], broadcast) float64.  ``desired_goal`` takes
+        the goal and observation slots 9..11 ``goal - achieved_goal`` (float64, rounded once for a
+        float32 observation); nothing else changes (reset(goal=...) draws new joints).  Not with
+        the HER feed: an open episode's goal would change under it.  Returns the obs dict."""
+        torch = _torch()
+        if self._her is not None:
+            raise RuntimeError("set_goal: not with the HER feed (an open episode's goal would change under it)")
+        g = torch.as_tensor(goal, dtype=torch.float64, device=self.device).reshape(-1, 3)
+        if g.shape[0] == 1 and self.num_envs > 1:
+            g = g.expand(self.num_envs, 3)
+        if g.shape[0] != self.num_envs:
+            raise ValueError("goal must be [%d, 3] or [1, 3]" % self.num_envs)
+        g = g.contiguous()
+        m = None if mask is None else torch.as_tensor(mask, device=self.device).to(torch.uint8).reshape(-1).contiguous()
+        if m is not None and m.shape[0] != self.num_envs:
+            raise ValueError("mask must be [%d]" % self.num_envs)
+        self._keep_goal = (g, m)   # keep alive until the kernel has consumed them
+        rc = self.lib.ctr_set_goal(self.cfg, self._batch, _abi.ptr(m), _abi.ptr(g), _abi.ptr(self.obs),
+                                   _abi.stream_ptr(stream, self.device.index))
+        _abi.check(rc, "ctr_set_goal")
+        return self._obs_dict()
+
+    def follow_ineligible(self, fused=True):
+        """None if follow can run this env's steps, else the reason it cannot (``fused=False``: its
+        Python loop, which the period kernel's modes do not limit)."""
+        if self.autoreset:
+            return ("not with auto-reset (a done env is not reset in a follow): build an evaluation env with "
+                    "autoreset=False")
+        if self._her is not None:
+            return "not with the HER feed"
+        if not fused:
+            return None
+        why = self._period_ineligible()
+        if why:
+            return why
+        if not self._tail_eligible():          # ctr_follow refuses that mode as ctr_rollout does
+            return ("not for the compliant model's scipy RK45 with y pre-curvature (the kernel would spill to "
+                    "scratch); use set_goal(), act() and step_raw()")
+        return None
+
+    def follow(self, actor, waypoints, hold, reach=False, steps=None, fused=True, record_actions=False, stream=None,
+               resume=None):
+        """Every env follows its own waypoint path with the policy: waypoints [N, K, 3] float64 (as
+        for dls_ik_path; ``ctr_reach_amd.paths`` makes them).  An env chases waypoint c for at most
+        ``hold`` steps, with ``reach`` only until a step's ``success`` (the goal tolerance, read
+        from the schedule at the call), then moves its goal to waypoint c + 1; past the last
+        waypoint it keeps stepping towards it.  ``steps`` (default K * hold) closed-loop steps run
+        as ctr_follow launches of up to CTR_STEP_MANY_MAX steps: the goal changes happen inside
+        the fused period kernel, between two steps.  ``fused=False`` is the same loop in Python
+        (set_goal + act + step_raw per step), bit for bit.  No auto-reset, no noise and no HER in a
+        follow: RuntimeError (the env untouched) for an env built with autoreset=True, with the HER
+        feed and, for the fused launches, wherever rollout() refuses (follow_ineligible).
+
+        Returns a FollowResult: tip [N, K, 3], error [N, K], steps [N, K], reached [N, K] recorded
+        when an env left a waypoint (NaN / 0 for a waypoint it has not left), cursor [N] and held
+        [N], and actions [steps, N, 6] with ``record_actions``.  ``resume``: the FollowResult of an
+        earlier call with the same waypoints, to go on from its cursors (it is updated and returned)."""
+        torch = _torch()
+        why = self.follow_ineligible(fused)
+        if why:
+            raise RuntimeError("follow: " + why)
+        if actor.blob is None or actor.blob.device != self.obs.device:
+            raise ValueError("follow: the actor must be on %s" % self.device)
+        if actor.in_dim != self.obs_dim + 6:
+            raise ValueError("the actor takes %d inputs, this env's rows have %d" % (actor.in_dim, self.obs_dim + 6))
+        n, dev = self.num_envs, self.device
+        wp = torch.as_tensor(waypoints, dtype=torch.float64, device=dev)
+        if wp.dim() != 3 or wp.shape[0] != n or wp.shape[1] < 1 or wp.shape[2] != 3:
+            raise ValueError("follow: waypoints must be [%d, K, 3] with K >= 1" % n)
+        K, hold, reach = int(wp.shape[1]), int(hold), bool(reach)
+        if hold < 1:
+            raise ValueError("follow: hold must be >= 1")
+        steps = K * hold if steps is None else int(steps)
+        if steps < 0:
+            raise ValueError("follow: steps must be >= 0")
+        wp_kn = wp.transpose(0, 1).contiguous()          # env-minor [K, N, 3]: what the kernel reads
+        res = resume if resume is not None else FollowResult(n, K, dev)
+        if res.tip.shape != (n, K, 3) or res.cursor.device != dev:
+            raise ValueError("follow: resume is not the result of a follow of these waypoints")
+        res.actions = torch.empty((steps, n, 6), dtype=torch.float32, device=dev) if record_actions else None
+        self.cfg.tol = float(self.goal_tolerance.get_tol())
+        if not fused:
+            self._follow_eager(actor, wp_kn, hold, reach, steps, res, stream)
+            return res
+        fw = _abi.CtrFollow(_abi.ptr(wp_kn), K, hold, int(reach), 0, _abi.ptr(res.cursor), _abi.ptr(res.held),
+                            _abi.ptr(res._tip), _abi.ptr(res._error), _abi.ptr(res._steps), _abi.ptr(res._reached))
+        self._keep_follow = (wp_kn, res)                 # keep alive until the kernels have consumed them
+        sp = _abi.stream_ptr(stream, self.device.index)
+        i = 0
+        while i < steps:
+            k = min(steps - i, _abi.CTR_STEP_MANY_MAX)
+            if self.pool_depth:                # never past the refill that falls due
+                k = min(k, self.refill_interval - self._steps_since_refill)
+            rec = res.actions[i].data_ptr() if res.actions is not None else None
+            rc = self.lib.ctr_follow(self.cfg, self._batch, actor._struct, fw, k, self._out, rec, sp)
+            _abi.check(rc, "ctr_follow")
+            self.fused_launches += 1
+            if self.pool_depth:
+                self._steps_since_refill += k
+                if self._steps_since_refill >= self.refill_interval:
+                    self.refill_pool(stream)
+            i += k
+        return res
+
+    def _follow_eager(self, actor, wp_kn, hold, reach, steps, res, stream):
+        """follow(fused=False): the goal changes, the actor, the step and the bookkeeping as launches
+        of their own (stream-ordered: the host reads nothing between them)."""
+        torch = _torch()
+        n, K = self.num_envs, wp_kn.shape[0]
+        ar = torch.arange(n, device=self.device)
+        tip, err = res._tip.view(K * n, 3), res._error.view(K * n)
+        cnt, rch = res._steps.view(K * n), res._reached.view(K * n)
+        c, h = res.cursor, res.held
+        with torch.cuda.stream(_current_stream(stream, self.device)):
+            for i in range(steps):
+                at = torch.clamp(c, max=K - 1).long()
+                self.set_goal(wp_kn[at, ar], mask=(c < K) & (h == 0), stream=stream)
+                a = self.act(actor, stream=stream)
+                self.step_raw(a, stream)
+                if res.actions is not None:
+                    res.actions[i].copy_(a)
+                on = c < K
+                h += on.to(torch.int32)
+                ok = self.success.bool()
+                adv = on & ((h >= hold) | (ok if reach else torch.zeros_like(ok)))
+                w = at * n + ar                  # the env's own entry of waypoint c: no two envs share one
+                tip[w] = torch.where(adv[:, None], self.achieved_goal, tip[w])
+                err[w] = torch.where(adv, self.error, err[w])
+                cnt[w] = torch.where(adv, h, cnt[w])
+                rch[w] = torch.where(adv, ok.to(torch.uint8), rch[w])
+                c += adv.to(torch.int32)
+                h.masked_fill_(adv, 0)
+
     # ------------------------------------------------------------------ data collection (policy.ExploreNoise)
     def explore(self, actions, noise, stream=None):
         """``noise`` (policy.ExploreNoise) on ``actions`` [N, 6] for the step the envs take next
@@ -957,6 +1093,31 @@ class CtrReachVecEnv(object):
 
     def close(self):
         pass
+
+
+class FollowResult(object):
+    """What CtrReachVecEnv.follow recorded, as device tensors: per env and waypoint, written when the
+    env left the waypoint, ``tip`` [N, K, 3] float64 (NaN before), ``error`` [N, K] float32 (NaN
+    before), ``steps`` [N, K] int32 and ``reached`` [N, K] uint8 (0 before); per env ``cursor`` [N]
+    (the waypoint it is on, K: past the end) and ``held`` [N] (steps spent on it) int32; ``actions``
+    [steps, N, 6] float32 of the last call, or None.  The [N, K] tensors are views of the env-minor
+    [K, N] arrays the kernel writes."""
+
+    def __init__(self, n, K, device):
+        torch = _torch()
+        nan = float("nan")
+        self._tip = torch.full((K, n, 3), nan, dtype=torch.float64, device=device)
+        self._error = torch.full((K, n), nan, dtype=torch.float32, device=device)
+        self._steps = torch.zeros((K, n), dtype=torch.int32, device=device)
+        self._reached = torch.zeros((K, n), dtype=torch.uint8, device=device)
+        self.cursor = torch.zeros(n, dtype=torch.int32, device=device)
+        self.held = torch.zeros(n, dtype=torch.int32, device=device)
+        self.actions = None
+
+    tip = property(lambda self: self._tip.transpose(0, 1))
+    error = property(lambda self: self._error.transpose(0, 1))
+    steps = property(lambda self: self._steps.transpose(0, 1))
+    reached = property(lambda self: self._reached.transpose(0, 1))
 
 
 class StepGraph(object):

@@ -38,6 +38,10 @@
  *                       DDPG under HER: NormalActionNoise clipped to the action box and
  *                       random_exploration on the policy's action; ctr_collect together with the
  *                       env.step calls and the replay wrapper's add() of that loop
+ *   ctr_set_goal / ctr_follow
+ *                       the policy side of the path-following comparisons of src/ (a trained policy
+ *                       against dls_ik_position_only along line / circle / helix waypoints): the
+ *                       goal moved from waypoint to waypoint between the env.step calls
  *   ctr_domain_params   Model.current_sys_parameters after randomize_parameters
  *                                                                          envs/model.py:20-28, model_utils.py:5-35
  *   ctr_her_open / ctr_her_record / ctr_her_sample
@@ -602,6 +606,61 @@ int ctr_explore(const ctr_batch_t *batch, const ctr_explore_t *explore, const fl
 int ctr_collect(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *actor,
                 const ctr_explore_t *explore, const ctr_her_t *her, int32_t k, const ctr_step_out_t *out,
                 int32_t autoreset, const ctr_rollout_aux_t *aux, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Retargeting and waypoint following (entry points added within ABI 17: no existing entry point or
+ * struct changes, so the number stays; a caller that needs them looks the symbols up).  The policy
+ * side of the reference's line / circle / helix path comparisons of src/, whose IK side is
+ * ctr_ik_dls.
+ *
+ * ctr_set_goal: a new desired goal for the environments with mask[e] != 0 (mask NULL = all), the
+ * joints kept (ctr_reset with a goal draws them anew).  For each such env
+ *     batch->desired_goal[e][k] = goal[e][k]                                    (k = 0..2, f64)
+ *     obs[e][9 + k]             = goal[e][k] - batch->achieved_goal[e][k]
+ * one f64 subtraction each, stored as every observation is: rounded once to f32, or kept as f64
+ * with cfg->obs_f64.  Nothing else changes: not the joints, t, epoch, system, the other observation
+ * slots, the reward / done / success / error rows or the pool.  goal [n][3] f64, obs [n][obs_dim]
+ * (device).  Refused (CTR_EINVAL, before any HIP call): a NULL argument other than mask, a
+ * missing batch buffer, a batch size out of range.  n = 0 is a no-op. */
+int ctr_set_goal(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const uint8_t *mask, const double *goal,
+                 void *obs, void *stream);
+
+/* ctr_follow: ctr_rollout (CTR_AUTORESET_OFF, no statistics) in which every env walks its own list
+ * of K waypoints.  Per-env state: the cursor c (the waypoint the env is on, K = past the end) and
+ * held (steps spent on waypoint c); both read when the launch starts and written back, so launches
+ * chain.  Each env, on each of the k steps:
+ *   1. if c < K and held == 0: the env is retargeted to waypoints[c][e] as ctr_set_goal does it
+ *      (the desired_goal row and observation slots 9..11 are stored); the actor's row of this step
+ *      has (float)(g - ag) in slots 9..11 and (float)g in its goal slots
+ *   2. a = actor(row), then the step, exactly as ctr_rollout takes it with CTR_AUTORESET_OFF
+ *   3. if c < K: held += 1; the env advances if held >= hold, or if reach is set and the step's
+ *      success is set.  On an advance tip[c][e] = achieved goal (3 x f64), err[c][e] = the step's
+ *      f32 error, steps[c][e] = held, reached[c][e] = success; then c += 1, held = 0
+ *   4. an env with c == K keeps stepping towards its last waypoint and records nothing
+ * Afterwards the batch, the step outputs, cursor, held, the four per-waypoint arrays and `actions`
+ * are exactly what k rounds of
+ *     ctr_set_goal(mask = (c < K && held == 0), goal = waypoints[c]);  ctr_actor(actor, row, ...);
+ *     ctr_step(cfg, batch, actions, out, CTR_AUTORESET_OFF, ...);  the bookkeeping of 3.
+ * would have left, bit for bit.  No auto-reset, no noise and no HER in a follow; entries of the
+ * per-waypoint arrays whose waypoint no env left in this call are not written.
+ * Refused (CTR_EINVAL, before any HIP call) wherever ctr_rollout is, with its messages (so also for
+ * the compliant model's scipy RK45 with a y pre-curvature, for the lane-pair and 8-lane group modes,
+ * with packed rows or the gather, on an in_dim mismatch and when the LDS does not suffice, with the
+ * byte counts); for a NULL follow, waypoints, cursor or held; K < 1, hold < 1, reach not 0 or 1.
+ * n = 0 is a no-op. */
+typedef struct ctr_follow_t {
+    const double *waypoints;    /* [K][n][3] device: env-minor, so a wave whose lanes share a    */
+                                /* cursor loads one span                                         */
+    int32_t K, hold, reach, pad;
+    int32_t *cursor, *held;     /* [n] device, in and out; cursor in 0..K, held in 0..hold-1    */
+    double  *tip;               /* [K][n][3] or NULL: the tip when the env left the waypoint     */
+    float   *err;               /* [K][n]    or NULL: the f32 error of that step                 */
+    int32_t *steps;             /* [K][n]    or NULL: the steps the env spent on the waypoint    */
+    uint8_t *reached;           /* [K][n]    or NULL: that step's success                        */
+} ctr_follow_t;
+int ctr_follow(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *actor,
+               const ctr_follow_t *follow, int32_t k, const ctr_step_out_t *out,
+               float *actions /* [k][n][6] or NULL */, void *stream);
 
 /* CtrReachEnv.reset for the environments with mask[i] != 0 (mask NULL = all).
  * goal [n][3] or NULL (sample a goal), system [n] or NULL (sample uniformly).
