@@ -31,6 +31,23 @@ NUM_TUBES = 3
 EXT_TOL = 1e-3    # obs.py:14
 ZERO_TOL = 1e-4   # obs.py:16
 RK4_REFILL_BUDGET = 32   # resumable refill, fixed-step RK4: RK4 steps per reset FK and refill
+# kernel mode 1 fills the register file in k_step_many already: no period kernel that does more
+_SPILLS = ("not for the compliant model's scipy RK45 with y pre-curvature (the kernel would spill to "
+           "scratch); use ")
+
+
+def period_chunk(remaining, since_refill, pool_depth, refill_interval, pooled_steps, autoreset, pool_full):
+    """(k, mode) of the next period-kernel launch, ``since_refill`` steps after a refill: at most
+    CTR_STEP_MANY_MAX of the ``remaining`` steps, never past the refill that falls due and, with
+    auto-reset, never past ``pooled_steps`` (every step as step_raw would run it: POOLED).  k = 0:
+    the next step's resets are not all in the pool (step_raw would sweep; no period kernel does)."""
+    k = min(remaining, _abi.CTR_STEP_MANY_MAX)
+    if pool_depth:
+        k = min(k, refill_interval - since_refill)
+    if not autoreset:
+        return k, _abi.AUTORESET_OFF
+    k = min(k, pooled_steps - since_refill)
+    return (k if k >= 1 and pool_full else 0), _abi.AUTORESET_POOLED
 
 
 def _torch():
@@ -143,6 +160,10 @@ class CtrReachVecEnv(object):
             raise ValueError("obs_dtype must be float32 or float64")
         self.obs_dtype = torch.float64 if obs_dtype in ("float64", torch.float64) else torch.float32
         self.cfg.obs_f64 = int(self.obs_dtype == torch.float64)
+        # the kernels' MODE (make_kcfg): y pre-curvature | fixed-step RK4 << 1 | rigid model << 2
+        has_uy = any(self.cfg.systems[s].Uy[i] != 0.0 for s in range(self.n_systems) for i in range(3))
+        self._kmode = (int(has_uy) | (solver[0] == _abi.CTR_INTEGRATOR_RK4) << 1
+                       | (solver[2] == _abi.CTR_MODEL_RIGID) << 2)
         n, dev = self.num_envs, self.device
         f32, f64, i32 = torch.float32, torch.float64, torch.int32
         init = np.asarray(kw["initial_joints"], dtype=np.float64)
@@ -379,12 +400,7 @@ class CtrReachVecEnv(object):
         """One step of every env.  actions: [N,6] float32 device tensor.  Returns
         (obs dict, reward [N] f32, done [N] bool, info dict of tensors).  Returned tensors are
         views of persistent buffers, overwritten by the next call."""
-        torch = _torch()
-        if actions.dtype != torch.float32 or actions.device != self.device or not actions.is_contiguous():
-            actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
-        if actions.shape != (self.num_envs, 6):
-            raise ValueError("actions must be [%d, 6]" % self.num_envs)
-        self._last_actions = actions
+        actions = self._last_actions = self._as_actions(actions)
         self.step_raw(actions, stream)
         info = {"is_success": self.success.bool(), "error": self.error,
                 "terminal_observation": self.terminal_obs, "terminal_achieved_goal": self.terminal_achieved,
@@ -439,12 +455,62 @@ class CtrReachVecEnv(object):
             _abi.check(rc, "ctr_step")
         if her is not None and not her.fused:  # ctr_her_record from the step's outputs
             her._record(actions, stream)
-        if self.autoreset:
+        self._stepped(1, stream)
+
+    def _stepped(self, k, stream, refilled=False):
+        """The host bookkeeping after k launched steps: the miss counters' parity, the refill
+        schedule and the refill that falls due (``refilled``: the launch ran it itself)."""
+        if self.autoreset and k % 2:
             self._batch.work_parity ^= 1
-        if self.pool_depth:
-            self._steps_since_refill += 1
+        if refilled:
+            self.refills += 1                  # the period's refill has run (no ctr_pool_refill launch)
+        elif self.pool_depth:
+            self._steps_since_refill += k
             if self._steps_since_refill >= self.refill_interval:
                 self.refill_pool(stream)
+
+    def _run_periods(self, who, steps, launch, stream):
+        """``steps`` steps as period-kernel launches, cut by period_chunk, with step_raw's host
+        bookkeeping after each.  ``launch(i, k, mode, whole_period)`` launches steps i .. i + k - 1
+        (``whole_period``: pooled, from a refill to the next one) and returns whether it also ran
+        the period's refill."""
+        i = 0
+        while i < steps:
+            since = self._steps_since_refill
+            k, mode = period_chunk(steps - i, since, self.pool_depth, self.refill_interval, self._pooled_steps(),
+                                   self.autoreset, self._pool_full)
+            if k < 1:
+                raise RuntimeError("%s: the next step's resets are not all in the pool" % who)
+            whole_period = mode == _abi.AUTORESET_POOLED and since == 0 and k == self.refill_interval
+            refilled = launch(i, k, mode, whole_period)
+            self.fused_launches += 1
+            self._stepped(k, stream, refilled)
+            i += k
+
+    def _as_actions(self, actions, who=None):
+        """``actions`` as a contiguous float32 [N, 6] tensor on the env's device: converted where
+        they are not (step, explore), or with ``who`` refused (step_many: nothing is copied)."""
+        torch = _torch()
+        ready = actions.dtype == torch.float32 and actions.device == self.device and actions.is_contiguous()
+        if who and not (ready and actions.shape == (self.num_envs, 6)):
+            raise ValueError("%s: actions must be contiguous float32 [%d, 6] tensors on %s" % (who, self.num_envs, self.device))
+        if not ready:
+            actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        if actions.shape != (self.num_envs, 6):
+            raise ValueError("actions must be [%d, 6]" % self.num_envs)
+        return actions
+
+    def _check_actor(self, who, actor):
+        # who None: act(), where the actor moves the rows to its own device
+        if who and (actor.blob is None or actor.blob.device != self.obs.device):
+            raise ValueError("%s: the actor must be on %s" % (who, self.device))
+        if actor.in_dim != self.obs_dim + 6:
+            raise ValueError("the actor takes %d inputs, this env's rows have %d" % (actor.in_dim, self.obs_dim + 6))
+
+    def _system_rows(self, system, m):
+        # ``system`` (one index, or one per row) as the [m] int32 device rows the FK entry points read
+        torch = _torch()
+        return None if system is None else torch.as_tensor(system, dtype=torch.int32, device=self.device).reshape(-1).expand(m).contiguous()
 
     def step_many_ineligible(self):
         """None if step_many can run this env's steps, else the reason it cannot."""
@@ -456,12 +522,10 @@ class CtrReachVecEnv(object):
         # what keeps an env from every period kernel (step_many, rollout, collect)
         if self._push_gather is not None or self.packed_bufs is not None:
             return "not with packed outputs or the push gather"
-        if self.integrator == "rk4":
-            if self.model == "rigid":
-                return "not for the rigid model's fixed-step RK4 (8-lane group step)"
-            uy = any(self.cfg.systems[s].Uy[i] != 0.0 for s in range(self.n_systems) for i in range(3))
-            if not uy:
-                return "not for the compliant model's fixed-step RK4 (lane-pair step)"
+        if self._kmode & 6 == 6:
+            return "not for the rigid model's fixed-step RK4 (8-lane group step)"
+        if self._kmode == 2:
+            return "not for the compliant model's fixed-step RK4 (lane-pair step)"
         if self.autoreset and not (self.pool_depth and self._pool_full):
             return "auto-reset needs the reset pool, full (every reset of the steps precomputed)"
         return None
@@ -469,9 +533,7 @@ class CtrReachVecEnv(object):
     def _tail_eligible(self):
         # ctr_step_period refuses the compliant model's scipy RK45 with y pre-curvature (its kernel
         # would spill to scratch): that mode keeps ctr_step_many and the refill launch
-        if self.integrator == "rk45_scipy" and self.model == "compliant":
-            return not any(self.cfg.systems[s].Uy[i] != 0.0 for s in range(self.n_systems) for i in range(3))
-        return True
+        return self._kmode != 1
 
     def step_many(self, actions, stream=None):
         """len(actions) consecutive step_raw calls, each refill period's steps as one launch
@@ -488,52 +550,25 @@ class CtrReachVecEnv(object):
         the step kernel's tail and no ctr_pool_refill launch; the results are the same bits.
         Every step of the call is judged with the goal tolerance the schedule holds when step_many
         is called, as the step_raw calls would (no update can fall between them)."""
-        torch = _torch()
         why = self.step_many_ineligible()
         if why:
             raise RuntimeError("step_many: " + why)
         self.cfg.tol = float(self.goal_tolerance.get_tol())
-        actions = list(actions)
-        for a in actions:
-            if (a.dtype != torch.float32 or a.device != self.device or not a.is_contiguous()
-                    or a.shape != (self.num_envs, 6)):
-                raise ValueError("step_many: actions must be contiguous float32 [%d, 6] tensors on %s"
-                                 % (self.num_envs, self.device))
+        actions = [self._as_actions(a, "step_many") for a in actions]
         sp = _abi.stream_ptr(stream, self.device.index)
-        i = 0
-        while i < len(actions):
-            k = min(len(actions) - i, _abi.CTR_STEP_MANY_MAX)
-            if self.pool_depth:                # never past the refill that falls due
-                k = min(k, self.refill_interval - self._steps_since_refill)
-            mode = _abi.AUTORESET_OFF
-            if self.autoreset:                 # every step of the launch as step_raw would run it: POOLED
-                k = min(k, self._pooled_steps() - self._steps_since_refill)
-                if k < 1 or not self._pool_full:
-                    raise RuntimeError("step_many: the next step's resets are not all in the pool")
-                mode = _abi.AUTORESET_POOLED
+
+        def launch(i, k, mode, whole_period):
             seq = _abi.CtrActionSeq()
             for j in range(k):
                 seq.a[j] = actions[i + j].data_ptr()
-            # a whole period (from a refill to the next one): its refill in the same launch
-            tail = (self.tail_refill and mode == _abi.AUTORESET_POOLED and self._steps_since_refill == 0
-                    and k == self.refill_interval and self._tail_eligible())
-            if tail:
-                rc = self.lib.ctr_step_period(self.cfg, self._batch, seq, k, self._out, sp)
-                _abi.check(rc, "ctr_step_period")
+            if whole_period and self.tail_refill and self._tail_eligible():    # its refill in the same launch
+                _abi.check(self.lib.ctr_step_period(self.cfg, self._batch, seq, k, self._out, sp), "ctr_step_period")
                 self.tail_launches += 1
-            else:
-                rc = self.lib.ctr_step_many(self.cfg, self._batch, seq, k, self._out, mode, sp)
-                _abi.check(rc, "ctr_step_many")
-            self.fused_launches += 1
-            if self.autoreset and k % 2:
-                self._batch.work_parity ^= 1
-            if tail:
-                self.refills += 1              # the period's refill has run (no ctr_pool_refill launch)
-            elif self.pool_depth:
-                self._steps_since_refill += k
-                if self._steps_since_refill >= self.refill_interval:
-                    self.refill_pool(stream)
-            i += k
+                return True
+            _abi.check(self.lib.ctr_step_many(self.cfg, self._batch, seq, k, self._out, mode, sp), "ctr_step_many")
+            return False
+
+        self._run_periods("step_many", len(actions), launch, stream)
 
     # ------------------------------------------------------------------ closed loop (policy.MlpActor)
     def actor_rows(self):
@@ -546,8 +581,7 @@ class CtrReachVecEnv(object):
     def act(self, actor, stream=None):
         """The actor's actions on the env's current observation: [N, 6] float32 (one ctr_actor
         launch)."""
-        if actor.in_dim != self.obs_dim + 6:
-            raise ValueError("the actor takes %d inputs, this env's rows have %d" % (actor.in_dim, self.obs_dim + 6))
+        self._check_actor(None, actor)
         return actor(self.actor_rows(), stream=stream)
 
     ROLLOUT_STATS = (("episodes", "int32"), ("successes", "int32"), ("error_sum", "float64"), ("length_sum", "int32"))
@@ -575,19 +609,16 @@ class CtrReachVecEnv(object):
         why = self.step_many_ineligible()
         if why:
             raise RuntimeError("rollout: " + why)
-        return self._closed_loop("rollout", actor, steps, record_actions, stream)
+        return self._closed_loop("rollout", actor, steps, record_actions, stream, lambda k, mode, aux, sp: _abi.check(
+            self.lib.ctr_rollout(self.cfg, self._batch, actor._struct, k, self._out, mode, aux, sp), "ctr_rollout"))
 
-    def _closed_loop(self, who, actor, steps, record_actions, stream, collect=False, noise=None):
-        """rollout()'s launches and host bookkeeping, and with ``collect`` collect()'s (ctr_collect in
-        place of ctr_rollout)."""
+    def _closed_loop(self, who, actor, steps, record_actions, stream, call):
+        """What rollout() and collect() share: the checks of the actor, the statistics, the recorded
+        actions and the periods; ``call(k, mode, aux, sp)`` launches one period's k steps."""
         torch = _torch()
         if not self._tail_eligible():          # ctr_rollout refuses that mode as ctr_step_period does
-            raise RuntimeError("%s: not for the compliant model's scipy RK45 with y pre-curvature (the kernel "
-                               "would spill to scratch); use act() and step_raw()" % who)
-        if actor.blob is None or actor.blob.device != self.obs.device:
-            raise ValueError("%s: the actor must be on %s" % (who, self.device))
-        if actor.in_dim != self.obs_dim + 6:
-            raise ValueError("the actor takes %d inputs, this env's rows have %d" % (actor.in_dim, self.obs_dim + 6))
+            raise RuntimeError(who + ": " + _SPILLS + "act() and step_raw()")
+        self._check_actor(who, actor)
         steps = int(steps)
         rec = torch.empty((steps, self.num_envs, 6), dtype=torch.float32, device=self.device) if record_actions else None
         aux = _abi.CtrRolloutAux()
@@ -598,33 +629,12 @@ class CtrReachVecEnv(object):
                 setattr(aux, k, self.rollout_stats[k].data_ptr())
         self.cfg.tol = float(self.goal_tolerance.get_tol())
         sp = _abi.stream_ptr(stream, self.device.index)
-        i = 0
-        while i < steps:
-            k = min(steps - i, _abi.CTR_STEP_MANY_MAX)
-            if self.pool_depth:                # never past the refill that falls due
-                k = min(k, self.refill_interval - self._steps_since_refill)
-            mode = _abi.AUTORESET_OFF
-            if self.autoreset:                 # every step of the launch as step_raw would run it: POOLED
-                k = min(k, self._pooled_steps() - self._steps_since_refill)
-                if k < 1 or not self._pool_full:
-                    raise RuntimeError("%s: the next step's resets are not all in the pool" % who)
-                mode = _abi.AUTORESET_POOLED
+
+        def launch(i, k, mode, whole_period):
             aux.actions = rec[i].data_ptr() if rec is not None else None
-            if collect:
-                rc = self.lib.ctr_collect(self.cfg, self._batch, actor._struct, noise._struct if noise is not None else None,
-                                          self._her._h, k, self._out, mode, aux, sp)
-                _abi.check(rc, "ctr_collect")
-            else:
-                rc = self.lib.ctr_rollout(self.cfg, self._batch, actor._struct, k, self._out, mode, aux, sp)
-                _abi.check(rc, "ctr_rollout")
-            self.fused_launches += 1
-            if self.autoreset and k % 2:
-                self._batch.work_parity ^= 1
-            if self.pool_depth:
-                self._steps_since_refill += k
-                if self._steps_since_refill >= self.refill_interval:
-                    self.refill_pool(stream)
-            i += k
+            call(k, mode, aux, sp)
+
+        self._run_periods(who, steps, launch, stream)
         return rec
 
     # ------------------------------------------------------------------ waypoint following (paths)
@@ -666,8 +676,7 @@ class CtrReachVecEnv(object):
         if why:
             return why
         if not self._tail_eligible():          # ctr_follow refuses that mode as ctr_rollout does
-            return ("not for the compliant model's scipy RK45 with y pre-curvature (the kernel would spill to "
-                    "scratch); use set_goal(), act() and step_raw()")
+            return _SPILLS + "set_goal(), act() and step_raw()"
         return None
 
     def follow(self, actor, waypoints, hold, reach=False, steps=None, fused=True, record_actions=False, stream=None,
@@ -691,10 +700,7 @@ class CtrReachVecEnv(object):
         why = self.follow_ineligible(fused)
         if why:
             raise RuntimeError("follow: " + why)
-        if actor.blob is None or actor.blob.device != self.obs.device:
-            raise ValueError("follow: the actor must be on %s" % self.device)
-        if actor.in_dim != self.obs_dim + 6:
-            raise ValueError("the actor takes %d inputs, this env's rows have %d" % (actor.in_dim, self.obs_dim + 6))
+        self._check_actor("follow", actor)
         n, dev = self.num_envs, self.device
         wp = torch.as_tensor(waypoints, dtype=torch.float64, device=dev)
         if wp.dim() != 3 or wp.shape[0] != n or wp.shape[1] < 1 or wp.shape[2] != 3:
@@ -718,20 +724,12 @@ class CtrReachVecEnv(object):
                             _abi.ptr(res._tip), _abi.ptr(res._error), _abi.ptr(res._steps), _abi.ptr(res._reached))
         self._keep_follow = (wp_kn, res)                 # keep alive until the kernels have consumed them
         sp = _abi.stream_ptr(stream, self.device.index)
-        i = 0
-        while i < steps:
-            k = min(steps - i, _abi.CTR_STEP_MANY_MAX)
-            if self.pool_depth:                # never past the refill that falls due
-                k = min(k, self.refill_interval - self._steps_since_refill)
+
+        def launch(i, k, mode, whole_period):  # (no auto-reset in a follow: the mode is always OFF)
             rec = res.actions[i].data_ptr() if res.actions is not None else None
-            rc = self.lib.ctr_follow(self.cfg, self._batch, actor._struct, fw, k, self._out, rec, sp)
-            _abi.check(rc, "ctr_follow")
-            self.fused_launches += 1
-            if self.pool_depth:
-                self._steps_since_refill += k
-                if self._steps_since_refill >= self.refill_interval:
-                    self.refill_pool(stream)
-            i += k
+            _abi.check(self.lib.ctr_follow(self.cfg, self._batch, actor._struct, fw, k, self._out, rec, sp), "ctr_follow")
+
+        self._run_periods("follow", steps, launch, stream)
         return res
 
     def _follow_eager(self, actor, wp_kn, hold, reach, steps, res, stream):
@@ -769,11 +767,7 @@ class CtrReachVecEnv(object):
         (their current clocks and reset numbers), in the box ``action_space.high``: one ctr_explore
         launch.  A contiguous float32 tensor on the env's device is perturbed in place (anything
         else is converted, that is copied, first); returns the perturbed tensor, for step()."""
-        torch = _torch()
-        if actions.dtype != torch.float32 or actions.device != self.device or not actions.is_contiguous():
-            actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
-        if actions.shape != (self.num_envs, 6):
-            raise ValueError("actions must be [%d, 6]" % self.num_envs)
+        actions = self._as_actions(actions)
         scale = (ctypes.c_float * 6)(*[float(v) for v in self.action_space.high])
         rc = self.lib.ctr_explore(self._batch, noise._struct, scale, _abi.ptr(actions),
                                   _abi.stream_ptr(stream, self.device.index))
@@ -803,7 +797,9 @@ class CtrReachVecEnv(object):
         why = self.collect_ineligible()
         if why:
             raise RuntimeError("collect: " + why)
-        return self._closed_loop("collect", actor, steps, record_actions, stream, collect=True, noise=noise)
+        return self._closed_loop("collect", actor, steps, record_actions, stream, lambda k, mode, aux, sp: _abi.check(
+            self.lib.ctr_collect(self.cfg, self._batch, actor._struct, noise._struct if noise is not None else None,
+                                 self._her._h, k, self._out, mode, aux, sp), "ctr_collect"))
 
     def capture_steps(self, actions, stream=None):
         """Capture len(actions) consecutive steps (step_raw, with the pool refills that fall due)
@@ -851,7 +847,7 @@ class CtrReachVecEnv(object):
         torch = _torch()
         q = torch.as_tensor(joints, dtype=torch.float32, device=self.device).reshape(-1, 6).contiguous()
         m = q.shape[0]
-        s = None if system is None else torch.as_tensor(system, dtype=torch.int32, device=self.device).reshape(-1).expand(m).contiguous()
+        s = self._system_rows(system, m)
         tip = torch.empty((m, 3), dtype=torch.float64, device=self.device)
         stats = torch.zeros((m, 4), dtype=torch.int32, device=self.device) if return_stats else None
         status = torch.zeros(m, dtype=torch.int32, device=self.device)
@@ -882,7 +878,7 @@ class CtrReachVecEnv(object):
         torch = _torch()
         q = torch.as_tensor(joints, dtype=torch.float32, device=self.device).reshape(-1, 6).contiguous()
         m = q.shape[0]
-        s = None if system is None else torch.as_tensor(system, dtype=torch.int32, device=self.device).reshape(-1).expand(m).contiguous()
+        s = self._system_rows(system, m)
         tb = None
         if tables is not None:
             tb = torch.as_tensor(tables, dtype=torch.float64, device=self.device).reshape(m, 18).contiguous()
@@ -902,7 +898,7 @@ class CtrReachVecEnv(object):
         torch = _torch()
         q = torch.as_tensor(joints, dtype=torch.float64, device=self.device).reshape(-1, 6).contiguous()
         m = q.shape[0]
-        s = None if system is None else torch.as_tensor(system, dtype=torch.int32, device=self.device).reshape(-1).expand(m).contiguous()
+        s = self._system_rows(system, m)
         tip = torch.empty((m, 3), dtype=torch.float64, device=self.device)
         jac = torch.empty((m, 3, 6), dtype=torch.float64, device=self.device)
         rc = self.lib.ctr_jacobian(_abi.ptr(q), _abi.ptr(s), m, self.cfg, float(eps), _abi.ptr(tip), _abi.ptr(jac),
@@ -934,7 +930,7 @@ class CtrReachVecEnv(object):
         q_in = torch.as_tensor(q0, dtype=torch.float64, device=self.device).reshape(-1, 6).contiguous()
         if q_in.shape[0] != m:
             raise ValueError("q0 must be [M, 6] for targets [M, ...]")
-        s = None if system is None else torch.as_tensor(system, dtype=torch.int32, device=self.device).reshape(-1).expand(m).contiguous()
+        s = self._system_rows(system, m)
         q = torch.empty((m, k, 6), dtype=torch.float64, device=self.device)
         err = torch.empty((m, k), dtype=torch.float64, device=self.device)
         iters = torch.empty((m, k), dtype=torch.int32, device=self.device)
@@ -1123,6 +1119,8 @@ class FollowResult(object):
 class StepGraph(object):
     """A captured sequence of CtrReachVecEnv steps (CtrReachVecEnv.capture_steps)."""
 
+    COUNTERS = ("refills", "sweeps", "packed_seq", "fused_launches", "tail_launches")   # the env's, that a step moves
+
     def __init__(self, env, actions, stream=None):
         torch = _torch()
         k = len(actions)
@@ -1140,7 +1138,7 @@ class StepGraph(object):
         self.actions = [a for a in actions]
         self.stream = stream if stream is not None else torch.cuda.Stream(device=env.device)
         self.stream.wait_stream(torch.cuda.current_stream(env.device))
-        refills, sweeps, seq, fused, tails = env.refills, env.sweeps, env.packed_seq, env.fused_launches, env.tail_launches
+        before = {c: getattr(env, c) for c in self.COUNTERS}
         # each refill period as one launch (step_many) where the env allows it
         self.fused = env.fused_period and env.step_many_ineligible() is None
         self.graph = torch.cuda.CUDAGraph()
@@ -1150,12 +1148,12 @@ class StepGraph(object):
             else:
                 for a in self.actions:
                     env.step_raw(a, self.stream)
-        self.refills_per_replay = env.refills - refills
-        self.fused_per_replay = env.fused_launches - fused
-        self.tails_per_replay = env.tail_launches - tails
+        self.refills_per_replay = env.refills - before["refills"]
+        self.fused_per_replay = env.fused_launches - before["fused_launches"]
+        self.tails_per_replay = env.tail_launches - before["tail_launches"]
         # the capture launched nothing: its host bookkeeping is undone, replay() redoes it
-        env.refills, env.sweeps, env.packed_seq, env.fused_launches = refills, sweeps, seq, fused
-        env.tail_launches = tails
+        for c, v in before.items():
+            setattr(env, c, v)
         assert env._steps_since_refill == 0 or not env.pool_depth
 
     def replay(self):

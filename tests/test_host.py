@@ -99,13 +99,18 @@ def test_autoreset_modes_and_pool_requeue_validate_without_gpu():
 
 
 def test_struct_layout_matches_header(tmp_path):
-    """ctypes mirrors of the ABI structs have the C sizes and every field offset (gcc on the header)."""
+    """ctypes mirrors of the ABI structs have the C sizes and every field offset, and the constants
+    _abi.py copies by hand have the header's values (gcc on the header)."""
     from ctr_reach_amd import _abi
     structs = [(_abi.CtrSystem, "ctr_system_t"), (_abi.CtrTubeRaw, "ctr_tube_raw_t"),
                (_abi.CtrEnvConfig, "ctr_env_config_t"), (_abi.CtrBatch, "ctr_batch_t"),
                (_abi.CtrStepOut, "ctr_step_out_t"), (_abi.CtrHer, "ctr_her_t"), (_abi.CtrHerBatch, "ctr_her_batch_t"),
                (_abi.CtrCopy, "ctr_copy_t"), (_abi.CtrGatherPush, "ctr_gather_push_t"),
-               (_abi.CtrPoolSlot, "ctr_pool_slot_t")]
+               (_abi.CtrPoolSlot, "ctr_pool_slot_t"), (_abi.CtrActionSeq, "ctr_action_seq_t"), (_abi.CtrIk, "ctr_ik_t"),
+               (_abi.CtrActor, "ctr_actor_t"), (_abi.CtrRolloutAux, "ctr_rollout_aux_t"),
+               (_abi.CtrExplore, "ctr_explore_t"), (_abi.CtrFollow, "ctr_follow_t")]
+    mirrors = {v for v in vars(_abi).values() if isinstance(v, type) and issubclass(v, ctypes.Structure)}
+    assert mirrors == {cls for cls, _ in structs}      # no mirror is left unchecked
     lines, want = [], []
     for cls, cname in structs:
         lines.append('  printf("%%zu\\n", sizeof(%s));' % cname)
@@ -113,6 +118,16 @@ def test_struct_layout_matches_header(tmp_path):
         for fname, _ in cls._fields_:
             lines.append('  printf("%%zu\\n", offsetof(%s, %s));' % (cname, fname))
             want.append(getattr(cls, fname).offset)
+    # every integer constant of _abi.py (CTR_*, and AUTORESET_* for CTR_AUTORESET_*)
+    consts = {("CTR_" + k if k.startswith("AUTORESET_") else k): v for k, v in vars(_abi).items()
+              if k.startswith(("CTR_", "AUTORESET_")) and isinstance(v, int)}
+    for family, count in (("CTR_ABI_VERSION", 1), ("_MAX", 8), ("CTR_HER_SCAN_TILE", 1), ("CTR_INTEGRATOR_", 2),
+                          ("CTR_MODEL_", 2), ("CTR_STATUS_", 5), ("CTR_HER_F", 2), ("CTR_HER_E", 1),
+                          ("CTR_GATHER_E_", 4), ("CTR_AUTORESET_", 3)):
+        assert sum(family in k for k in consts) >= count, family         # the scan above found them
+    for k, v in consts.items():
+        lines.append('  printf("%%lld\\n", (long long)(%s));' % k)
+        want.append(v)
     prog = tmp_path / "layout.c"
     prog.write_text("#include <stdio.h>\n#include <stddef.h>\n#include \"ctr_reach_amd.h\"\nint main(void) {\n"
                     + "\n".join(lines) + "\n  return 0; }\n")
