@@ -1,0 +1,129 @@
+"""DDPG + HER on CtrReachVecEnv: the loop the device-side pieces were built for, small and readable
+(not a tuned trainer).
+
+Every iteration
+  1. collects ``steps_per_iter`` steps of every env with the current policy and exploration noise,
+     recorded into the HER store: ``venv.collect(actor, steps, noise)``, one launch per refill period;
+  2. draws relabelled batches on the device: ``her.sample(batch_size)``;
+  3. makes the DDPG critic and actor updates in torch on them, and the Polyak update of the targets;
+  4. refreshes the kernels' copy of the policy from the learner's parameters: ``actor.load_(policy)``,
+     one launch, no copy to the host.
+Everything is ordered on one stream and nothing is read back inside an iteration; the losses are
+read once at its end.
+
+The policy is ``Linear, ReLU, ..., Linear, Tanh`` (what ``MlpActor.from_torch`` takes) on
+HERGoalEnvWrapper's flat row, and the action is ``scale * policy(row)`` with ``scale`` the action
+space's high, so the critic sees actions in [-1, 1].  HER follows the reference's config
+(ctr_reach_amd/her.py): strategy ``future``, ``n_sampled_goal`` 4, batch 256.  The learning rates,
+``tau`` and ``gamma`` are stable-baselines DDPG's defaults; the noise is this example's choice.
+
+The first episodes are cut short at random (the envs start with clocks spread over the time limit):
+episodes enter the store when they end, so otherwise it would stay empty for a whole time limit and
+then fill in bursts.  While the store is empty ``sample`` returns zero rows, which teach nothing and
+harm nothing.
+
+usage: python examples/train_ddpg_her.py [--num-envs N] [--iterations I] [--steps-per-iter S]
+           [--batch-size B] [--updates-per-iter U] [--hidden 64,64] [--seed 0] [--device cuda]"""
+import argparse
+import os
+import sys
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "gym-ctr-reach_amd"))
+from ctr_reach_amd import CtrReachVecEnv  # noqa: E402
+from ctr_reach_amd.policy import ExploreNoise, MlpActor  # noqa: E402
+
+GAMMA, TAU, ACTOR_LR, CRITIC_LR = 0.99, 0.001, 1e-4, 1e-3
+N_SAMPLED_GOAL, STRATEGY = 4, "future"
+SIGMA, RANDOM_EPS = 0.2, 0.3
+
+
+def mlp(n_in, hidden, n_out, tanh):
+    dims = [n_in] + list(hidden)
+    mods = []
+    for a, b in zip(dims[:-1], dims[1:]):
+        mods += [nn.Linear(a, b), nn.ReLU()]
+    mods.append(nn.Linear(dims[-1], n_out))
+    if tanh:
+        mods.append(nn.Tanh())
+    return nn.Sequential(*mods)
+
+
+def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, updates_per_iter=40, hidden=(64, 64), seed=0,
+         device="cuda"):
+    device = torch.device(device)
+    torch.manual_seed(seed)
+    venv = CtrReachVecEnv(num_envs, device=device, seed=seed)
+    her = venv.enable_her(n_sampled_goal=N_SAMPLED_GOAL, goal_selection_strategy=STRATEGY)
+    venv.reset()
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    venv.t.copy_(torch.randint(0, venv.max_steps_per_episode, (num_envs,), generator=g, dtype=torch.int32))
+
+    d = venv.obs_dim + 6
+    scale = torch.tensor(venv.action_space.high, dtype=torch.float32, device=device)
+    policy, critic = mlp(d, hidden, 6, True).to(device), mlp(d + 6, hidden, 1, False).to(device)
+    policy_targ, critic_targ = mlp(d, hidden, 6, True).to(device), mlp(d + 6, hidden, 1, False).to(device)
+    policy_targ.load_state_dict(policy.state_dict())
+    critic_targ.load_state_dict(critic.state_dict())
+    for p in list(policy_targ.parameters()) + list(critic_targ.parameters()):
+        p.requires_grad_(False)
+    policy_opt = torch.optim.Adam(policy.parameters(), lr=ACTOR_LR)
+    critic_opt = torch.optim.Adam(critic.parameters(), lr=CRITIC_LR)
+
+    actor = MlpActor.from_torch(policy, venv.action_space.high, device)      # once; load_ from here on
+    noise = ExploreNoise(SIGMA, random_eps=RANDOM_EPS, seed=seed)
+    losses = []
+    for it in range(iterations):
+        venv.collect(actor, steps_per_iter, noise)
+        critic_sum = torch.zeros((), device=device)
+        policy_sum = torch.zeros((), device=device)
+        for _ in range(updates_per_iter):
+            batch = her.sample(batch_size)
+            obs, next_obs = batch["obs"], batch["next_obs"]
+            with torch.no_grad():
+                q_next = critic_targ(torch.cat((next_obs, policy_targ(next_obs)), dim=1)).squeeze(1)
+                target = batch["reward"] + GAMMA * (1.0 - batch["done"]) * q_next
+            critic_loss = F.mse_loss(critic(torch.cat((obs, batch["action"] / scale), dim=1)).squeeze(1), target)
+            critic_opt.zero_grad(set_to_none=True)
+            critic_loss.backward()
+            critic_opt.step()
+            policy_loss = -critic(torch.cat((obs, policy(obs)), dim=1)).mean()
+            policy_opt.zero_grad(set_to_none=True)
+            policy_loss.backward()         # (the critic's gradients from this pass are dropped by its zero_grad)
+            policy_opt.step()
+            with torch.no_grad():
+                for net, targ in ((policy, policy_targ), (critic, critic_targ)):
+                    for p, pt in zip(net.parameters(), targ.parameters()):
+                        pt.lerp_(p, TAU)
+            critic_sum += critic_loss.detach()
+            policy_sum += policy_loss.detach()
+        actor.load_(policy)
+        # the iteration's only host read
+        losses.append((critic_sum.item() / max(updates_per_iter, 1), policy_sum.item() / max(updates_per_iter, 1)))
+    return dict(actor=actor, policy=policy, critic=critic, policy_targ=policy_targ, critic_targ=critic_targ,
+                losses=losses, rollout_stats=venv.rollout_stats, venv=venv, her=her)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--num-envs", type=int, default=4096)
+    ap.add_argument("--iterations", type=int, default=50)
+    ap.add_argument("--steps-per-iter", type=int, default=20)
+    ap.add_argument("--batch-size", type=int, default=256)
+    ap.add_argument("--updates-per-iter", type=int, default=40)
+    ap.add_argument("--hidden", default="64,64", help="hidden widths, multiples of 32")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", default="cuda")
+    args = ap.parse_args()
+    out = main(args.num_envs, args.iterations, args.steps_per_iter, args.batch_size, args.updates_per_iter,
+               tuple(int(w) for w in args.hidden.split(",")), args.seed, args.device)
+    for it, (c, p) in enumerate(out["losses"]):
+        print("iteration %3d: critic loss %.4g, policy loss %.4g" % (it, c, p))
+    stats = out["rollout_stats"]
+    episodes, successes = int(stats["episodes"].sum()), int(stats["successes"].sum())
+    print("%d episodes finished, %d reached their goal; %d rows in the HER store" % (episodes, successes, len(out["her"])))

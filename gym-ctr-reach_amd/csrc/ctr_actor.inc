@@ -1,6 +1,6 @@
 // ctr_actor.inc -- the deterministic MLP actor (ctr_actor, and the actor of k_rollout): its
-// arithmetic, the packed weight blob and the host-side packer.  Included by ctr_kernels.hip inside
-// its anonymous namespace.
+// arithmetic, the packed weight blob and its packers, on the host (actor_pack) and on the device
+// (k_actor_load).  Included by ctr_kernels.hip inside its anonymous namespace.
 //
 // The network (include/ctr_reach_amd.h, "MLP actor"): 1..3 hidden layers of width 32..256 (multiples
 // of 32) on the flat row x[in_dim] = [observation, achieved_goal, desired_goal], zero-padded to 32:
@@ -44,13 +44,14 @@ struct ActorK {
 };
 
 // k index of element j of lane half h in k-step S of layer l (see the header comment).
-inline int actor_k_of(int l, int S, int h, int j)
+__host__ __device__ inline int actor_k_of(int l, int S, int h, int j)
 {
     if (l == 0) return 16 * S + 8 * h + j;
     return 32 * (S >> 1) + 16 * (S & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
 }
 
-inline uint16_t actor_bf16_bits(float f)
+// float -> bf16 bits in integer arithmetic (host and device: k_actor_load gives the host packer's bits)
+__host__ __device__ inline uint16_t actor_bf16_bits(float f)
 {
     uint32_t u;
     memcpy(&u, &f, 4);
@@ -131,6 +132,84 @@ int actor_pack(const ctr_actor_t *a, const float *const *W, const float *const *
         memcpy(out + ak.b_off[l], b[l], (size_t)rows * 4);
     }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The packer on the device (ctr_actor_load): actor_pack's bytes from device-resident parameters, so
+// that a trainer refreshes the blob after an optimiser step without a copy to the host.  One thread
+// per 16 B of the blob: a weight fragment (lane `lane` of k-step S of tile T of layer l) or four
+// bias floats.  Every byte of the blob is written, the padding as zero; no thread reads what another
+// wrote.
+struct ActorSrc {
+    const float *W[ACTOR_LAYERS];      // device, row-major [out][in]
+    const float *b[ACTOR_LAYERS];      // device, [out]
+};
+
+typedef float actor_f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // a parameter tensor may start at any float
+
+__global__ __launch_bounds__(BLOCK) void k_actor_load(ActorK ak, ActorSrc src, void *__restrict__ blob)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= ak.bytes / 16) return;
+    const uint32_t byte = 16 * i;
+    const bool bias = byte >= ak.b_off[0];
+    // the item's layer and its place in it; the arrays by constant index (they are kernel arguments)
+    int l = 0, rows = 0, cols = 0;
+    uint32_t off = 0;
+    const float *W = nullptr, *b = nullptr;
+    #pragma unroll
+    for (int m = 0; m < ACTOR_LAYERS; ++m) {
+        const uint32_t start = bias ? ak.b_off[m] : ak.w_off[m];
+        if (m <= ak.n_hidden && byte >= start) {
+            l = m;
+            off = byte - start;
+            rows = m < ak.n_hidden ? 32 * ak.tiles[m] : 6;
+            cols = m == 0 ? ak.in_dim : 32 * ak.tiles[m - 1];
+            W = src.W[m];
+            b = src.b[m];
+        }
+    }
+    uint4 out = {0u, 0u, 0u, 0u};
+    if (bias) {
+        // copied as bits; rows is 6 in the output layer, so the tail is guarded per float
+        const int e = (int)(off / 4);
+        const uint32_t *bb = reinterpret_cast<const uint32_t *>(b);
+        uint32_t v[4];
+        #pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = e + t < rows ? bb[e + t] : 0u;
+        out = {v[0], v[1], v[2], v[3]};
+    } else {
+        const int ksteps = l == 0 ? 2 : cols / 16;
+        const int f = (int)(off / 16), lane = f & 63, h = lane >> 5, ts = f >> 6;
+        const int T = ts / ksteps, S = ts - T * ksteps, row = 32 * T + (lane & 31);
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (row < rows) {
+            const float *wr = W + (size_t)row * cols;
+            if (l == 0) {
+                // eight consecutive floats of a 19- or 20-float row
+                #pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int k = actor_k_of(0, S, h, j);
+                    if (k < cols) v[j] = wr[k];
+                }
+            } else {
+                // two runs of four (cols is a multiple of 32, so both lie inside the row)
+                const actor_f32x4u a0 = *reinterpret_cast<const actor_f32x4u *>(wr + actor_k_of(l, S, h, 0));
+                const actor_f32x4u a1 = *reinterpret_cast<const actor_f32x4u *>(wr + actor_k_of(l, S, h, 4));
+                #pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    v[j] = a0[j];
+                    v[4 + j] = a1[j];
+                }
+            }
+        }
+        uint32_t w[4];
+        #pragma unroll
+        for (int j = 0; j < 4; ++j)
+            w[j] = (uint32_t)actor_bf16_bits(v[2 * j]) | ((uint32_t)actor_bf16_bits(v[2 * j + 1]) << 16);    // +0 -> 0
+        out = {w[0], w[1], w[2], w[3]};
+    }
+    static_cast<uint4 *>(blob)[i] = out;
 }
 
 // ------------------------------------------------------------------------------------------

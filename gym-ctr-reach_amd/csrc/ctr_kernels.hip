@@ -16,6 +16,8 @@
 //   k_rollout     k_step_many with each step's action computed by an MLP actor from the observation
 //                 the step before left in the lane's registers (ctr_rollout, at the end of the file)
 //   k_actor       the MLP actor alone, one row per lane, its blob staged into LDS (ctr_actor.inc)
+//   k_actor_load  the actor's blob packed on the device from f32 parameters, one thread per 16 B
+//                 (ctr_actor_load; ctr_actor.inc)
 //   k_collect     k_rollout with exploration noise on each action and each step recorded into the HER
 //                 store (ctr_collect, at the end of the file)
 //   k_explore     the exploration noise alone, one env per lane (ctr_explore; explore_lane, ctr_device.hpp)
@@ -3068,6 +3070,24 @@ int64_t ctr_actor_blob_bytes(const ctr_actor_t *a)
 int ctr_actor_pack(const ctr_actor_t *a, const float *const *W, const float *const *b, void *blob_host)
 {
     return actor_pack(a, W, b, blob_host);
+}
+
+int ctr_actor_load(const ctr_actor_t *a, const float *const *W, const float *const *b, void *stream)
+{
+    ActorK ak;
+    if (int r = actor_layout(a, &ak)) return r;
+    if (!W || !b) return fail(CTR_EINVAL, "ctr_actor_load: W or b is NULL");
+    ActorSrc src = {};
+    for (int l = 0; l <= a->n_hidden; ++l) {
+        if (!W[l] || !b[l]) return fail(CTR_EINVAL, "ctr_actor_load: NULL layer among W[0..n_hidden], b[0..n_hidden]");
+        src.W[l] = W[l];
+        src.b[l] = b[l];
+    }
+    if (!a->blob) return fail(CTR_EINVAL, "actor: blob is NULL");
+    if (((uintptr_t)a->blob & 15u) != 0) return fail(CTR_EINVAL, "actor: blob must be 16-B aligned");
+    hipLaunchKernelGGL(k_actor_load, dim3(grid_for(ak.bytes / 16)), dim3(BLOCK), 0, (hipStream_t)stream, ak, src,
+                       const_cast<void *>(a->blob));
+    return hip_check("ctr_actor_load launch");
 }
 
 int ctr_actor(const ctr_actor_t *a, const float *rows, int64_t n, float *actions, float *logits, void *stream)

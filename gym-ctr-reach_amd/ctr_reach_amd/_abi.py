@@ -230,7 +230,7 @@ EXPORTED = ("ctr_abi_version", "ctr_last_error", "ctr_fk", "ctr_set_action", "ct
             "ctr_ipc_get_handle", "ctr_ipc_open", "ctr_ipc_close", "ctr_seqw_alloc", "ctr_seqw_free", "ctr_copy_list",
             "ctr_gather_wait", "ctr_gather_push", "ctr_gather_publish", "ctr_refill_carry_bytes", "ctr_step_many",
             "ctr_ik_dls", "ctr_step_period", "ctr_actor_blob_bytes", "ctr_actor_pack", "ctr_actor", "ctr_rollout",
-            "ctr_explore", "ctr_collect", "ctr_set_goal", "ctr_follow")
+            "ctr_explore", "ctr_collect", "ctr_set_goal", "ctr_follow", "ctr_actor_load")
 
 _lib = None
 
@@ -308,6 +308,8 @@ def load(path=None):
         L.ctr_set_goal.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch), _P, _P, _P, _P]
         L.ctr_follow.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch), ctypes.POINTER(CtrActor),
                                  ctypes.POINTER(CtrFollow), i32, ctypes.POINTER(CtrStepOut), _P, _P]
+    if hasattr(L, "ctr_actor_load"):               # added within ABI 17 (an older build lacks it)
+        L.ctr_actor_load.argtypes = [ctypes.POINTER(CtrActor), ctypes.POINTER(_P), ctypes.POINTER(_P), _P]
     if hasattr(L, "ctr_ik_dls"):                   # ABI 17
         L.ctr_ik_dls.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrIk), _P]
     if hasattr(L, "ctr_refill_carry_bytes"):       # ABI 12

@@ -5,6 +5,7 @@ reference's stable-baselines DDPG ``MlpPolicy`` actor on HERGoalEnvWrapper's fla
     actor = MlpActor([(W1, b1), (W2, b2), (Wout, bout)], scale=venv.action_space.high, device="cuda")
     actions = venv.act(actor)                 # one ctr_actor launch
     venv.rollout(actor, 20)                   # 20 closed-loop steps, one launch per refill period
+    actor.load_(policy_net)                   # new weights from device parameters, one ctr_actor_load launch
 
 ``MlpActor.emulate`` is the CPU reference of the actor's arithmetic (numpy, no GPU, no library).
 
@@ -29,7 +30,18 @@ class MlpActor(object):
     hidden layers (widths multiples of 32, at most 256) and the 6-row output layer; the first
     layer takes the flat row of obs_dim + 6 = 19 or 20 floats.  ``scale``: the action space's high
     (6 floats): action = scale * tanh(output).  ``device`` None keeps the actor on the host
-    (``emulate`` only)."""
+    (``emulate`` only).
+
+    Training: build the actor once from the learner's initial weights, then refresh it on the
+    device after every optimiser step with ``load_``: one launch on the learner's stream, no copy
+    to the host, no allocation (it can sit in a captured graph next to the update).
+
+        actor = MlpActor.from_torch(policy, venv.action_space.high, "cuda")
+        for it in range(iterations):
+            venv.collect(actor, steps, noise)
+            ...                                   # the learner's update of ``policy`` on her.sample(...)
+            optimiser.step()
+            actor.load_(policy)                   # ctr_actor_load: the blob now holds the new weights"""
 
     def __init__(self, layers, scale, device=None):
         ws, bs = [], []
@@ -58,6 +70,7 @@ class MlpActor(object):
             raise ValueError("scale must be 6 finite floats")
         self.device = None
         self.blob = None
+        self._sources = None            # load_'s device tensors (the blob was packed from them)
         self._struct = _abi.CtrActor()
         s = self._struct
         s.in_dim, s.n_hidden = self.in_dim, len(self.hidden)
@@ -71,24 +84,66 @@ class MlpActor(object):
     @classmethod
     def from_torch(cls, seq, scale, device=None):
         """From an ``nn.Sequential`` of Linear, ReLU, ..., Linear, Tanh."""
-        import torch.nn as nn
-        mods = list(seq)
-        if not mods or not isinstance(mods[-1], nn.Tanh):
-            raise ValueError("the actor ends with nn.Tanh")
-        layers = []
-        for i, m in enumerate(mods[:-1]):
-            if i % 2 == 0:
-                if not isinstance(m, nn.Linear) or m.bias is None:
-                    raise ValueError("module %d must be an nn.Linear with a bias" % i)
-                layers.append((m.weight.detach(), m.bias.detach()))
-            elif not isinstance(m, nn.ReLU):
-                raise ValueError("module %d must be an nn.ReLU" % i)
-        if len(mods) % 2:
-            raise ValueError("expected Linear, ReLU, ..., Linear, Tanh")
-        return cls(layers, scale, device)
+        return cls(_sequential_layers(seq), scale, device)
 
-    def _upload(self, device):
+    def load_(self, layers, stream=None, keep_host=False):
+        """Refresh the device blob in place from device-resident parameters (ctr_actor_load): one
+        launch on ``stream`` (default: the current stream), ordered like any other launch there; no
+        allocation, no copy to the host and no synchronisation, so it can be captured into a graph
+        (a replay packs whatever the parameters hold then).  ``layers``: [(W, b), ...] torch tensors
+        or an ``nn.Sequential`` as ``from_torch`` takes; every tensor on the actor's device,
+        float32, contiguous and of the actor's shapes, or ValueError is raised and the blob stays
+        (nothing is converted: a hidden copy would be a temporary the launch outlives).  The
+        tensors stay referenced by the actor until the next ``load_``.
+
+        The host copies (``weights``, ``biases``, ``packed``) would go stale: they are dropped, and
+        ``emulate`` / ``reference`` raise until a load with ``keep_host=True``, which copies the
+        sources back to the host and therefore SYNCHRONISES (not for a captured graph).  Returns
+        the actor."""
         import torch
+        if self.blob is None:
+            raise RuntimeError("the actor is on the host (MlpActor(..., device=None)): nothing to load into")
+        if isinstance(layers, torch.nn.Module):
+            layers = _sequential_layers(layers)
+        layers = [tuple(pair) for pair in layers]
+        dims = [self.in_dim] + self.hidden + [6]
+        if len(layers) != len(dims) - 1 or any(len(pair) != 2 for pair in layers):
+            raise ValueError("the actor has %d layers of (W, b)" % (len(dims) - 1))
+        src = []
+        for l, (W, b) in enumerate(layers):
+            pair = []
+            for name, t, shape in (("W", W, (dims[l + 1], dims[l])), ("b", b, (dims[l + 1],))):
+                what = "layer %d: %s" % (l, name)
+                if not isinstance(t, torch.Tensor):
+                    raise ValueError(what + " must be a torch tensor")
+                if t.device.type != self.device.type or (self.device.index is not None
+                                                         and t.device.index != self.device.index):
+                    raise ValueError("%s is on %s, the actor on %s" % (what, t.device, self.device))
+                if t.dtype != torch.float32:
+                    raise ValueError("%s must be float32, not %s" % (what, t.dtype))
+                if tuple(t.shape) != shape:
+                    raise ValueError("%s must be %s, not %s" % (what, list(shape), list(t.shape)))
+                if not t.is_contiguous():
+                    raise ValueError(what + " must be contiguous")
+                pair.append(t.detach())
+            src.append(tuple(pair))
+        n = len(src)
+        W = (_abi._P * n)(*[w.data_ptr() for w, _ in src])
+        b = (_abi._P * n)(*[v.data_ptr() for _, v in src])
+        rc = _abi.load().ctr_actor_load(self._struct, W, b, _abi.stream_ptr(stream, self.device.index))
+        _abi.check(rc, "ctr_actor_load")
+        self._sources = src
+        self.weights = self.biases = self.packed = None
+        if keep_host:
+            if stream is not None:
+                stream.synchronize()
+            self.weights = [np.ascontiguousarray(_to_numpy(w), dtype=np.float32) for w, _ in src]
+            self.biases = [np.ascontiguousarray(_to_numpy(v), dtype=np.float32) for _, v in src]
+            self.packed = self._pack_host()
+        return self
+
+    def _pack_host(self):
+        """ctr_actor_pack of the host copies -> the blob's bytes (numpy uint8)."""
         lib = _abi.load()
         nb = int(lib.ctr_actor_blob_bytes(self._struct))
         if nb < 0:
@@ -98,7 +153,11 @@ class MlpActor(object):
         W = (_abi._P * n)(*[w.ctypes.data for w in self.weights])
         b = (_abi._P * n)(*[v.ctypes.data for v in self.biases])
         _abi.check(lib.ctr_actor_pack(self._struct, W, b, host.ctypes.data), "ctr_actor_pack")
-        self.packed = host
+        return host
+
+    def _upload(self, device):
+        import torch
+        self.packed = host = self._pack_host()
         self.device = torch.device(device)
         self.blob = torch.from_numpy(host).to(self.device)
         if self.blob.data_ptr() % 16:
@@ -109,6 +168,7 @@ class MlpActor(object):
         """The actor's arithmetic (include/ctr_reach_amd.h) in numpy float64 with the kernel's bf16
         roundings: rows [n, in_dim] -> (actions [n, 6], logits [n, 6]) float64.  Also returns the
         intermediates in ``self.last_hidden`` (the bf16 activations of every hidden layer)."""
+        self._need_host()
         x = np.asarray(rows, dtype=np.float32).reshape(-1, self.in_dim)
         with np.errstate(invalid="ignore", over="ignore"):
             hi = bf16_round(x)
@@ -126,12 +186,17 @@ class MlpActor(object):
 
     def reference(self, rows):
         """The plain float64 MLP (no bf16 anywhere): actions [n, 6]."""
+        self._need_host()
         z = np.asarray(rows, dtype=np.float64).reshape(-1, self.in_dim)
         for l, (W, b) in enumerate(zip(self.weights, self.biases)):
             z = z @ W.astype(np.float64).T + b.astype(np.float64)
             if l < len(self.hidden):
                 z = np.maximum(z, 0.0)
         return self.scale.astype(np.float64) * np.tanh(z)
+
+    def _need_host(self):
+        if self.weights is None:
+            raise RuntimeError("the host copy of the weights was dropped by load_; load with keep_host=True")
 
     def __call__(self, rows, logits=False, stream=None):
         """ctr_actor: rows [n, in_dim] float32 device tensor -> actions [n, 6] (and the pre-tanh
@@ -237,6 +302,25 @@ class ExploreNoise(object):
         s = (self.sigma * box).astype(np.float64)                            # the float32 product
         gauss = np.clip(a32.astype(np.float64) + s * z, -box.astype(np.float64), box.astype(np.float64))
         return np.where(rnd[:, None], uniform.astype(np.float64), gauss)
+
+
+def _sequential_layers(seq):
+    """[(W, b), ...] (detached) of an ``nn.Sequential`` of Linear, ReLU, ..., Linear, Tanh."""
+    import torch.nn as nn
+    mods = list(seq)
+    if not mods or not isinstance(mods[-1], nn.Tanh):
+        raise ValueError("the actor ends with nn.Tanh")
+    layers = []
+    for i, m in enumerate(mods[:-1]):
+        if i % 2 == 0:
+            if not isinstance(m, nn.Linear) or m.bias is None:
+                raise ValueError("module %d must be an nn.Linear with a bias" % i)
+            layers.append((m.weight.detach(), m.bias.detach()))
+        elif not isinstance(m, nn.ReLU):
+            raise ValueError("module %d must be an nn.ReLU" % i)
+    if len(mods) % 2:
+        raise ValueError("expected Linear, ReLU, ..., Linear, Tanh")
+    return layers
 
 
 def _to_numpy(t):

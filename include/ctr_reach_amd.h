@@ -33,6 +33,8 @@
  *                       model.predict(obs, deterministic=True) of the stable-baselines DDPG MlpPolicy
  *                       actor in the evaluation loops of src/ (the loops behind evaluations*.csv),
  *                       ctr_rollout together with the env.step calls of those loops
+ *   ctr_actor_load      the learner's parameters into that actor after a policy update of the
+ *                       training pipeline (stable-baselines shares them inside one TensorFlow graph)
  *   ctr_explore / ctr_collect
  *                       the data collection of the reference's training pipeline, stable-baselines
  *                       DDPG under HER: NormalActionNoise clipped to the action box and
@@ -523,6 +525,13 @@ int64_t ctr_actor_blob_bytes(const ctr_actor_t *a);
  * the 6-row output layer) -> the packed blob in host memory, which the caller copies to the
  * device.  The weights are rounded to bf16 here, once.  scale and blob are not read. */
 int ctr_actor_pack(const ctr_actor_t *a, const float *const *W, const float *const *b, void *blob_host);
+/* The device-side ctr_actor_pack: W[l] / b[l] (l = 0..n_hidden) are DEVICE pointers to contiguous
+ * float32 [out, in] weights and [out] biases; a->blob (device, 16-B aligned, ctr_actor_blob_bytes())
+ * is overwritten with the same bytes ctr_actor_pack would give for those values, padding included.
+ * One launch on `stream`, nothing read back, no allocation: it can be captured into a graph, and a
+ * replay packs whatever the parameters hold then.  The caller orders it against launches that read
+ * the blob (the same stream does).  scale is not read.  (Added within ABI 17.) */
+int ctr_actor_load(const ctr_actor_t *a, const float *const *W, const float *const *b, void *stream);
 /* rows [n][in_dim] f32 -> actions [n][6] f32; logits [n][6] (the pre-tanh y) or NULL.  (device) */
 int ctr_actor(const ctr_actor_t *a, const float *rows, int64_t n, float *actions, float *logits, void *stream);
 
