@@ -1,6 +1,9 @@
 // ctr_actor.inc -- the deterministic MLP actor (ctr_actor, and the actor of k_rollout): its
-// arithmetic, the packed weight blob and its packers, on the host (actor_pack) and on the device
-// (k_actor_load).  Included by ctr_kernels.hip inside its anonymous namespace.
+// arithmetic, the packed weight blob and its packers, on the host (mlp_pack) and on the device
+// (k_actor_load).  Included by ctr_kernels.hip inside its anonymous namespace.  The MLP critic
+// (ctr_critic.inc) is the same code with another shape: a row of 25 or 26 floats [row, action]
+// (actor_tile<26>) and a one-row output layer without tanh (ActorK::out_rows = 1); layout, packers
+// and the column-tile function are shared, not copied.
 //
 // The network (include/ctr_reach_amd.h, "MLP actor"): 1..3 hidden layers of width 32..256 (multiples
 // of 32) on the flat row x[in_dim] = [observation, achieved_goal, desired_goal], zero-padded to 32:
@@ -39,7 +42,9 @@ struct ActorK {
     uint32_t w_off[ACTOR_LAYERS];      // byte offset of layer l's fragments
     uint32_t b_off[ACTOR_LAYERS];      // byte offset of layer l's biases
     uint32_t bytes;                    // whole blob
-    float scale[6];
+    float scale[6];                    // the actor's action box (the critic has none: zeros)
+    int32_t out_rows;                  // rows of the output layer: 6 (the actor), 1 (the critic); in what
+                                       // was padding, so the period kernels' arguments stay where they were
     const void *blob;
 };
 
@@ -59,38 +64,84 @@ __host__ __device__ inline uint16_t actor_bf16_bits(float f)
     return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);                      // nearest even
 }
 
-// The shape checks of every actor entry point; fills the layout.
-int actor_layout(const ctr_actor_t *a, ActorK *ak)
+// An MLP's shape as its public struct gives it (ctr_actor_t, ctr_critic_t): what the two networks
+// differ in is the input row and the rows of the output layer.
+struct MlpShape {
+    const char *who;                   // "actor" / "critic", in the messages
+    int in_extra;                      // in_dim = obs_dim + in_extra (obs_dim 13 or 14)
+    int out_rows;
+    int32_t in_dim, n_hidden;
+    const int32_t *width;
+};
+
+// The shape checks of every actor and critic entry point; fills the layout.
+int mlp_layout(const MlpShape &m, ActorK *ak)
 {
-    if (!a) return fail(CTR_EINVAL, "actor is NULL");
-    if (a->in_dim != 19 && a->in_dim != 20) return fail(CTR_EINVAL, "actor: in_dim must be obs_dim + 6 = 19 or 20");
-    if (a->n_hidden < 1 || a->n_hidden > CTR_ACTOR_MAX_HIDDEN)
-        return fail(CTR_EINVAL, "actor: n_hidden must be in 1..CTR_ACTOR_MAX_HIDDEN (3)");
-    for (int l = 0; l < a->n_hidden; ++l)
-        if (a->width[l] < 32 || a->width[l] > CTR_ACTOR_MAX_WIDTH || a->width[l] % 32)
-            return fail(CTR_EINVAL, "actor: every hidden width must be a multiple of 32 in 32..CTR_ACTOR_MAX_WIDTH (256)");
+    if (m.in_dim != 13 + m.in_extra && m.in_dim != 14 + m.in_extra) {
+        snprintf(g_err, sizeof g_err, "%s: in_dim must be obs_dim + %d = %d or %d", m.who, m.in_extra, 13 + m.in_extra,
+                 14 + m.in_extra);
+        return CTR_EINVAL;
+    }
+    if (m.n_hidden < 1 || m.n_hidden > CTR_ACTOR_MAX_HIDDEN) {
+        snprintf(g_err, sizeof g_err, "%s: n_hidden must be in 1..CTR_ACTOR_MAX_HIDDEN (3)", m.who);
+        return CTR_EINVAL;
+    }
+    for (int l = 0; l < m.n_hidden; ++l)
+        if (m.width[l] < 32 || m.width[l] > CTR_ACTOR_MAX_WIDTH || m.width[l] % 32) {
+            snprintf(g_err, sizeof g_err, "%s: every hidden width must be a multiple of 32 in 32..CTR_ACTOR_MAX_WIDTH (256)",
+                     m.who);
+            return CTR_EINVAL;
+        }
     memset(ak, 0, sizeof *ak);
-    ak->in_dim = a->in_dim;
-    ak->n_hidden = a->n_hidden;
+    ak->in_dim = m.in_dim;
+    ak->n_hidden = m.n_hidden;
+    ak->out_rows = m.out_rows;
     int64_t off = 0, wbytes = 0;
-    for (int l = 0; l <= a->n_hidden; ++l) {
-        const int tiles = l < a->n_hidden ? a->width[l] / 32 : 1;
-        const int ksteps = l == 0 ? 2 : a->width[l - 1] / 16;
+    for (int l = 0; l <= m.n_hidden; ++l) {
+        const int tiles = l < m.n_hidden ? m.width[l] / 32 : 1;
+        const int ksteps = l == 0 ? 2 : m.width[l - 1] / 16;
         ak->tiles[l] = tiles;
         ak->w_off[l] = (uint32_t)off;
         off += (int64_t)tiles * ksteps * 1024;
     }
     wbytes = off;
-    for (int l = 0; l <= a->n_hidden; ++l) {
+    for (int l = 0; l <= m.n_hidden; ++l) {
         ak->b_off[l] = (uint32_t)off;
         off += (int64_t)ak->tiles[l] * 32 * 4;
     }
     if (off > CTR_ACTOR_MAX_BYTES) {
-        snprintf(g_err, sizeof g_err, "actor: the packed network (%lld B of weights + %lld B of biases) exceeds "
-                 "CTR_ACTOR_MAX_BYTES = %d B of LDS", (long long)wbytes, (long long)(off - wbytes), CTR_ACTOR_MAX_BYTES);
+        snprintf(g_err, sizeof g_err, "%s: the packed network (%lld B of weights + %lld B of biases) exceeds "
+                 "CTR_ACTOR_MAX_BYTES = %d B of LDS", m.who, (long long)wbytes, (long long)(off - wbytes), CTR_ACTOR_MAX_BYTES);
         return CTR_EINVAL;
     }
     ak->bytes = (uint32_t)off;
+    return 0;
+}
+
+int actor_layout(const ctr_actor_t *a, ActorK *ak)
+{
+    if (!a) return fail(CTR_EINVAL, "actor is NULL");
+    return mlp_layout(MlpShape{"actor", 6, 6, a->in_dim, a->n_hidden, a->width}, ak);
+}
+
+int critic_layout(const ctr_critic_t *c, ActorK *ak)
+{
+    if (!c) return fail(CTR_EINVAL, "critic is NULL");
+    return mlp_layout(MlpShape{"critic", 12, 1, c->in_dim, c->n_hidden, c->width}, ak);
+}
+
+// The blob pointer of the entry points that read or write it.
+int mlp_blob(const char *who, const void *blob, ActorK *ak)
+{
+    if (!blob) {
+        snprintf(g_err, sizeof g_err, "%s: blob is NULL", who);
+        return CTR_EINVAL;
+    }
+    if (((uintptr_t)blob & 15u) != 0) {
+        snprintf(g_err, sizeof g_err, "%s: blob must be 16-B aligned", who);
+        return CTR_EINVAL;
+    }
+    ak->blob = blob;
     return 0;
 }
 
@@ -102,24 +153,32 @@ int actor_check(const ctr_actor_t *a, ActorK *ak)
         if (!isfinite(a->scale[i])) return fail(CTR_EINVAL, "actor: scale must be finite");
         ak->scale[i] = a->scale[i];
     }
-    if (!a->blob) return fail(CTR_EINVAL, "actor: blob is NULL");
-    if (((uintptr_t)a->blob & 15u) != 0) return fail(CTR_EINVAL, "actor: blob must be 16-B aligned");
-    ak->blob = a->blob;
-    return 0;
+    return mlp_blob("actor", a->blob, ak);
 }
 
-int actor_pack(const ctr_actor_t *a, const float *const *W, const float *const *b, void *blob_host)
+int critic_check(const ctr_critic_t *c, ActorK *ak)
 {
-    ActorK ak;
-    if (int r = actor_layout(a, &ak)) return r;
-    if (!W || !b || !blob_host) return fail(CTR_EINVAL, "ctr_actor_pack: NULL argument");
-    for (int l = 0; l <= a->n_hidden; ++l)
-        if (!W[l] || !b[l]) return fail(CTR_EINVAL, "ctr_actor_pack: NULL layer among W[0..n_hidden], b[0..n_hidden]");
+    if (int r = critic_layout(c, ak)) return r;
+    return mlp_blob("critic", c->blob, ak);
+}
+
+// The host packer of both networks (ctr_actor_pack, ctr_critic_pack: `fn`): the shape is ak's.
+int mlp_pack(const ActorK &ak, const char *fn, const float *const *W, const float *const *b, void *blob_host)
+{
+    if (!W || !b || !blob_host) {
+        snprintf(g_err, sizeof g_err, "%s: NULL argument", fn);
+        return CTR_EINVAL;
+    }
+    for (int l = 0; l <= ak.n_hidden; ++l)
+        if (!W[l] || !b[l]) {
+            snprintf(g_err, sizeof g_err, "%s: NULL layer among W[0..n_hidden], b[0..n_hidden]", fn);
+            return CTR_EINVAL;
+        }
     char *out = static_cast<char *>(blob_host);
     memset(out, 0, ak.bytes);
-    for (int l = 0; l <= a->n_hidden; ++l) {
-        const int rows = l < a->n_hidden ? a->width[l] : 6;
-        const int cols = l == 0 ? a->in_dim : a->width[l - 1];
+    for (int l = 0; l <= ak.n_hidden; ++l) {
+        const int rows = l < ak.n_hidden ? 32 * ak.tiles[l] : ak.out_rows;
+        const int cols = l == 0 ? ak.in_dim : 32 * ak.tiles[l - 1];
         const int ksteps = l == 0 ? 2 : cols / 16;
         for (int T = 0; T < ak.tiles[l]; ++T)
             for (int S = 0; S < ksteps; ++S)
@@ -135,8 +194,8 @@ int actor_pack(const ctr_actor_t *a, const float *const *W, const float *const *
 }
 
 // ------------------------------------------------------------------------------------------
-// The packer on the device (ctr_actor_load): actor_pack's bytes from device-resident parameters, so
-// that a trainer refreshes the blob after an optimiser step without a copy to the host.  One thread
+// The packer on the device (ctr_actor_load, ctr_critic_load): mlp_pack's bytes from device-resident
+// parameters, so that a trainer refreshes the blob after an optimiser step without a copy to the host.  One thread
 // per 16 B of the blob: a weight fragment (lane `lane` of k-step S of tile T of layer l) or four
 // bias floats.  Every byte of the blob is written, the padding as zero; no thread reads what another
 // wrote.
@@ -163,7 +222,7 @@ __global__ __launch_bounds__(BLOCK) void k_actor_load(ActorK ak, ActorSrc src, v
         if (m <= ak.n_hidden && byte >= start) {
             l = m;
             off = byte - start;
-            rows = m < ak.n_hidden ? 32 * ak.tiles[m] : 6;
+            rows = m < ak.n_hidden ? 32 * ak.tiles[m] : ak.out_rows;
             cols = m == 0 ? ak.in_dim : 32 * ak.tiles[m - 1];
             W = src.W[m];
             b = src.b[m];
@@ -171,7 +230,7 @@ __global__ __launch_bounds__(BLOCK) void k_actor_load(ActorK ak, ActorSrc src, v
     }
     uint4 out = {0u, 0u, 0u, 0u};
     if (bias) {
-        // copied as bits; rows is 6 in the output layer, so the tail is guarded per float
+        // copied as bits; rows is 6 or 1 in the output layer, so the tail is guarded per float
         const int e = (int)(off / 4);
         const uint32_t *bb = reinterpret_cast<const uint32_t *>(b);
         uint32_t v[4];
@@ -186,7 +245,7 @@ __global__ __launch_bounds__(BLOCK) void k_actor_load(ActorK ak, ActorSrc src, v
         if (row < rows) {
             const float *wr = W + (size_t)row * cols;
             if (l == 0) {
-                // eight consecutive floats of a 19- or 20-float row
+                // eight consecutive floats of an in_dim-float row (19 or 20; the critic's: 25 or 26)
                 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int k = actor_k_of(0, S, h, j);
@@ -210,6 +269,31 @@ __global__ __launch_bounds__(BLOCK) void k_actor_load(ActorK ak, ActorSrc src, v
         out = {w[0], w[1], w[2], w[3]};
     }
     static_cast<uint4 *>(blob)[i] = out;
+}
+
+// The launch of ctr_actor_load / ctr_critic_load (`fn`), after the shape checks: ak.blob not yet set.
+int mlp_load(ActorK &ak, const char *who, const char *fn, const void *blob, const float *const *W,
+             const float *const *b, void *stream)
+{
+    if (!W || !b) {
+        snprintf(g_err, sizeof g_err, "%s: W or b is NULL", fn);
+        return CTR_EINVAL;
+    }
+    ActorSrc src = {};
+    for (int l = 0; l <= ak.n_hidden; ++l) {
+        if (!W[l] || !b[l]) {
+            snprintf(g_err, sizeof g_err, "%s: NULL layer among W[0..n_hidden], b[0..n_hidden]", fn);
+            return CTR_EINVAL;
+        }
+        src.W[l] = W[l];
+        src.b[l] = b[l];
+    }
+    if (int r = mlp_blob(who, blob, &ak)) return r;
+    hipLaunchKernelGGL(k_actor_load, dim3(grid_for(ak.bytes / 16)), dim3(BLOCK), 0, (hipStream_t)stream, ak, src,
+                       const_cast<void *>(blob));
+    char what[64];
+    snprintf(what, sizeof what, "%s launch", fn);
+    return hip_check(what);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -273,111 +357,130 @@ __device__ __forceinline__ void actor_activate(const actor_f32x16 &acc, const fl
     }
 }
 
-// The whole network for the wave's 64 envs, one 32-env column tile after the other (the two tiles
-// together would hold twice the activations in registers: k_rollout then spills to scratch).
-// Every lane of the wave calls it (wave-uniform control flow): x = this lane's env's row (x[19] = 0
-// when in_dim is 19), lds = the staged blob.  Returns the lane's env's six pre-tanh outputs in y
-// and its actions in act.
-__device__ __forceinline__ void actor_wave(const ActorK &ak, const char *lds, const float x[20], float act[6], float y[6])
+
+// One 32-env column tile c of the wave through the network, up to the output layer's f32 tile with
+// its bias added (rows 0..3 of env 32c + r on lane r, rows 4..7 on lane 32 + r, in acc[0..3]).
+// Every lane of the wave calls it (wave-uniform control flow): x = this lane's env's row of NX
+// floats (NX = 20, the actor's: x[19] = 0 when in_dim is 19; NX = 26, the critic's: x[25] = 0 when
+// in_dim is 25), zero-padded to 32 here; lds = the staged blob.
+template <int NX>
+__device__ __forceinline__ actor_f32x16 actor_tile(const ActorK &ak, const char *lds, const float *x, int c)
 {
+    static_assert(NX > 16 && NX <= 32, "two k-steps over 32 padded inputs");
     const int lane = (int)(threadIdx.x & 63), h = lane >> 5, r = lane & 31;
     const actor_f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const actor_bf16x8 fzero = {0, 0, 0, 0, 0, 0, 0, 0};
+    // the input fragments of column tile c: k-step 0 = features 8h + j, k-step 1 = features
+    // 16 + 8h + j (those below NX exist: lane half 1 has none for the actor), each split into
+    // bf16 hi + lo
+    const int src = 32 * c + r;
+    actor_bf16x8 xh[2], xl[2];
+    xh[1] = fzero;
+    xl[1] = fzero;
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float v0 = __shfl(x[j], src), v1 = __shfl(x[8 + j], src);
+        const float v = h ? v1 : v0;
+        const __bf16 hi = (__bf16)v;
+        xh[0][j] = hi;
+        xl[0][j] = (__bf16)(v - (float)hi);
+    }
+    #pragma unroll
+    for (int j = 0; j < (NX - 16 < 8 ? NX - 16 : 8); ++j) {
+        const float v1 = __shfl(x[16 + j], src);
+        float v = h ? 0.f : v1;
+        if (24 + j < NX) {
+            const float v2 = __shfl(x[24 + j < NX ? 24 + j : 0], src);
+            v = h ? v2 : v1;
+        }
+        const __bf16 hi = (__bf16)v;
+        xh[1][j] = hi;
+        xl[1][j] = (__bf16)(v - (float)hi);
+    }
+    // activations: the k-step fragments of up to 256 features
+    actor_bf16x8 hin[2 * ACTOR_TILES], hout[2 * ACTOR_TILES];
+    #pragma unroll
+    for (int s = 0; s < 2 * ACTOR_TILES; ++s) hin[s] = hout[s] = fzero;
+    // layer 1: W1 x_hi + W1 x_lo, the same two fragments
+    {
+        const char *w = lds + ak.w_off[0];
+        const float *bias = reinterpret_cast<const float *>(lds + ak.b_off[0]);
+        #pragma unroll
+        for (int T = 0; T < ACTOR_TILES; ++T) {
+            if (T < ak.tiles[0]) {
+                const actor_bf16x8 a0 = actor_frag(w, 2 * T, lane), a1 = actor_frag(w, 2 * T + 1, lane);
+                actor_f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xh[0], zero, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xh[1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xl[0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xl[1], acc, 0, 0, 0);
+                actor_activate(acc, bias, T, h, hin[2 * T], hin[2 * T + 1]);
+            }
+        }
+    }
+    // the further hidden layers
+    #pragma unroll
+    for (int l = 1; l < CTR_ACTOR_MAX_HIDDEN; ++l) {
+        if (l < ak.n_hidden) {
+            const char *w = lds + ak.w_off[l];
+            const float *bias = reinterpret_cast<const float *>(lds + ak.b_off[l]);
+            const int tin = ak.tiles[l - 1];
+            #pragma unroll
+            for (int T = 0; T < ACTOR_TILES; ++T) {
+                if (T < ak.tiles[l]) {
+                    actor_f32x16 acc = zero;
+                    #pragma unroll
+                    for (int t = 0; t < ACTOR_TILES; ++t) {
+                        if (t < tin) {
+                            #pragma unroll
+                            for (int s = 2 * t; s < 2 * t + 2; ++s)
+                                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(actor_frag(w, T * 2 * tin + s, lane), hin[s],
+                                                                              acc, 0, 0, 0);
+                        }
+                    }
+                    actor_activate(acc, bias, T, h, hout[2 * T], hout[2 * T + 1]);
+                }
+            }
+            #pragma unroll
+            for (int s = 0; s < 2 * ACTOR_TILES; ++s) hin[s] = hout[s];
+        }
+    }
+    // the output layer: one tile, rows 0..5 (the critic: row 0); its bias is added before the lanes move
+    actor_f32x16 acc = zero;
+    {
+        const int lo = ak.n_hidden;               // 1..3: the offsets by constant index
+        const uint32_t wo = lo == 1 ? ak.w_off[1] : (lo == 2 ? ak.w_off[2] : ak.w_off[3]);
+        const uint32_t bo = lo == 1 ? ak.b_off[1] : (lo == 2 ? ak.b_off[2] : ak.b_off[3]);
+        const int tin = lo == 1 ? ak.tiles[0] : (lo == 2 ? ak.tiles[1] : ak.tiles[2]);
+        const char *w = lds + wo;
+        #pragma unroll
+        for (int t = 0; t < ACTOR_TILES; ++t) {
+            if (t < tin) {
+                #pragma unroll
+                for (int s = 2 * t; s < 2 * t + 2; ++s)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(actor_frag(w, s, lane), hin[s], acc, 0, 0, 0);
+            }
+        }
+        const float4 bb = *reinterpret_cast<const float4 *>(lds + bo + 16 * h);
+        acc[0] += bb.x;
+        acc[1] += bb.y;
+        acc[2] += bb.z;
+        acc[3] += bb.w;
+    }
+    return acc;
+}
+
+// The whole actor for the wave's 64 envs, one 32-env column tile after the other (the two tiles
+// together would hold twice the activations in registers: k_rollout then spills to scratch).
+// Every lane of the wave calls it: x as actor_tile<20> takes it.  Returns the lane's env's six
+// pre-tanh outputs in y.
+__device__ __forceinline__ void actor_logits(const ActorK &ak, const char *lds, const float x[20], float y[6])
+{
+    const int lane = (int)(threadIdx.x & 63), h = lane >> 5, r = lane & 31;
     #pragma unroll
     for (int i = 0; i < 6; ++i) y[i] = 0.f;
     #pragma unroll 1
     for (int c = 0; c < 2; ++c) {
-        // the input fragments of column tile c: k-step 0 = features 8h + j, k-step 1 = features
-        // 16 + 8h + j (only 16..19 exist), each split into bf16 hi + lo
-        const int src = 32 * c + r;
-        actor_bf16x8 xh[2], xl[2];
-        xh[1] = fzero;
-        xl[1] = fzero;
-        #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float v0 = __shfl(x[j], src), v1 = __shfl(x[8 + j], src);
-            const float v = h ? v1 : v0;
-            const __bf16 hi = (__bf16)v;
-            xh[0][j] = hi;
-            xl[0][j] = (__bf16)(v - (float)hi);
-        }
-        #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float v1 = __shfl(x[16 + j], src);
-            const float v = h ? 0.f : v1;
-            const __bf16 hi = (__bf16)v;
-            xh[1][j] = hi;
-            xl[1][j] = (__bf16)(v - (float)hi);
-        }
-        // activations: the k-step fragments of up to 256 features
-        actor_bf16x8 hin[2 * ACTOR_TILES], hout[2 * ACTOR_TILES];
-        #pragma unroll
-        for (int s = 0; s < 2 * ACTOR_TILES; ++s) hin[s] = hout[s] = fzero;
-        // layer 1: W1 x_hi + W1 x_lo, the same two fragments
-        {
-            const char *w = lds + ak.w_off[0];
-            const float *bias = reinterpret_cast<const float *>(lds + ak.b_off[0]);
-            #pragma unroll
-            for (int T = 0; T < ACTOR_TILES; ++T) {
-                if (T < ak.tiles[0]) {
-                    const actor_bf16x8 a0 = actor_frag(w, 2 * T, lane), a1 = actor_frag(w, 2 * T + 1, lane);
-                    actor_f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xh[0], zero, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xh[1], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, xl[0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xl[1], acc, 0, 0, 0);
-                    actor_activate(acc, bias, T, h, hin[2 * T], hin[2 * T + 1]);
-                }
-            }
-        }
-        // the further hidden layers
-        #pragma unroll
-        for (int l = 1; l < CTR_ACTOR_MAX_HIDDEN; ++l) {
-            if (l < ak.n_hidden) {
-                const char *w = lds + ak.w_off[l];
-                const float *bias = reinterpret_cast<const float *>(lds + ak.b_off[l]);
-                const int tin = ak.tiles[l - 1];
-                #pragma unroll
-                for (int T = 0; T < ACTOR_TILES; ++T) {
-                    if (T < ak.tiles[l]) {
-                        actor_f32x16 acc = zero;
-                        #pragma unroll
-                        for (int t = 0; t < ACTOR_TILES; ++t) {
-                            if (t < tin) {
-                                #pragma unroll
-                                for (int s = 2 * t; s < 2 * t + 2; ++s)
-                                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(actor_frag(w, T * 2 * tin + s, lane), hin[s],
-                                                                                  acc, 0, 0, 0);
-                            }
-                        }
-                        actor_activate(acc, bias, T, h, hout[2 * T], hout[2 * T + 1]);
-                    }
-                }
-                #pragma unroll
-                for (int s = 0; s < 2 * ACTOR_TILES; ++s) hin[s] = hout[s];
-            }
-        }
-        // the output layer: one tile, rows 0..5; its bias is added before the lanes move
-        actor_f32x16 acc = zero;
-        {
-            const int lo = ak.n_hidden;               // 1..3: the offsets by constant index
-            const uint32_t wo = lo == 1 ? ak.w_off[1] : (lo == 2 ? ak.w_off[2] : ak.w_off[3]);
-            const uint32_t bo = lo == 1 ? ak.b_off[1] : (lo == 2 ? ak.b_off[2] : ak.b_off[3]);
-            const int tin = lo == 1 ? ak.tiles[0] : (lo == 2 ? ak.tiles[1] : ak.tiles[2]);
-            const char *w = lds + wo;
-            #pragma unroll
-            for (int t = 0; t < ACTOR_TILES; ++t) {
-                if (t < tin) {
-                    #pragma unroll
-                    for (int s = 2 * t; s < 2 * t + 2; ++s)
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(actor_frag(w, s, lane), hin[s], acc, 0, 0, 0);
-                }
-            }
-            const float4 bb = *reinterpret_cast<const float4 *>(lds + bo + 16 * h);
-            acc[0] += bb.x;
-            acc[1] += bb.y;
-            acc[2] += bb.z;
-            acc[3] += bb.w;
-        }
+        const actor_f32x16 acc = actor_tile<20>(ak, lds, x, c);
         // rows 0..3 of env 32c + r sit on lane r, rows 4..5 on lane 32 + r; the env's own lane is
         // lane 32c + r
         #pragma unroll
@@ -386,6 +489,39 @@ __device__ __forceinline__ void actor_wave(const ActorK &ak, const char *lds, co
             y[i] = h == c ? v : y[i];
         }
     }
+}
+
+// ... and its actions in act.
+__device__ __forceinline__ void actor_wave(const ActorK &ak, const char *lds, const float x[20], float act[6], float y[6])
+{
+    actor_logits(ak, lds, x, y);
     #pragma unroll
     for (int i = 0; i < 6; ++i) act[i] = ak.scale[i] * tanhf(y[i]);
+}
+
+// The critic's input of an env: its flat row (row[19] = 0 for one system) and the six normalised
+// actions behind it, [row, a], 25 or 26 floats (x[25] = 0 for one system).
+__device__ __forceinline__ void critic_row(const float row[20], const float a[6], bool multi, float x[26])
+{
+    #pragma unroll
+    for (int k = 0; k < 19; ++k) x[k] = row[k];
+    x[19] = multi ? row[19] : a[0];
+    #pragma unroll
+    for (int i = 0; i < 5; ++i) x[20 + i] = multi ? a[i] : a[i + 1];
+    x[25] = multi ? a[5] : 0.f;
+}
+
+// The whole critic for the wave's 64 rows, as actor_logits: x as actor_tile<26> takes it.  Returns
+// the lane's row's Q (row 0 of the output tile: register 0 of lane r).
+__device__ __forceinline__ float critic_wave(const ActorK &ck, const char *lds, const float x[26])
+{
+    const int lane = (int)(threadIdx.x & 63), h = lane >> 5, r = lane & 31;
+    float q = 0.f;
+    #pragma unroll 1
+    for (int c = 0; c < 2; ++c) {
+        const actor_f32x16 acc = actor_tile<26>(ck, lds, x, c);
+        const float v = __shfl(acc[0], r);
+        q = h == c ? v : q;
+    }
+    return q;
 }

@@ -270,14 +270,18 @@ __global__ __launch_bounds__(BLOCK) void k_her_scan_tops(HerK hk, int64_t tiles)
 // ReplayBuffer.sample(batch_size): rows uniformly with replacement over the stored rows.  Row u
 // (one uniform integer below the stored-row count) is found by inverse CDF: the tile whose
 // offset range holds u, then the slot inside the tile, by binary search over the prefix sums.
-__global__ __launch_bounds__(BLOCK) void k_her_sample(HerK hk, int64_t B, uint64_t seed, uint64_t counter,
-                                                      ctr_her_batch_t out)
+//
+// her_sample_row: the row of this lane (row blockIdx.x * BLOCK + threadIdx.x of the batch), formed
+// into the block's LDS staging (s_obs / s_nobs [BLOCK][d], s_act [BLOCK][6]; a zero row when nothing
+// is stored or the lane is past B), its reward, done and index stored; rew and dn return the two
+// stored values.  Both samplers (k_her_sample, k_her_sample_td) call it, then a barrier, then
+// her_flush_batch.
+constexpr int HER_DMAX = 20;                              // obs_dim + 6 <= 20
+
+__device__ __forceinline__ void her_sample_row(const ctr_her_t &h, int64_t B, uint64_t seed, uint64_t counter,
+                                               const ctr_her_batch_t &out, float *s_obs, float *s_nobs, float *s_act,
+                                               float &rew, float &dn)
 {
-    const ctr_her_t &h = hk.h;
-    constexpr int DMAX = 20;                              // obs_dim + 6 <= 20
-    __shared__ __attribute__((aligned(16))) float s_obs[BLOCK * DMAX];
-    __shared__ __attribute__((aligned(16))) float s_nobs[BLOCK * DMAX];
-    __shared__ __attribute__((aligned(16))) float s_act[BLOCK * 6];
     const int64_t i0 = (int64_t)blockIdx.x * BLOCK;
     const int64_t i = i0 + threadIdx.x;
     const bool live = i < B;
@@ -315,7 +319,8 @@ __global__ __launch_bounds__(BLOCK) void k_her_sample(HerK hk, int64_t B, uint64
     }
     float *so = s_obs + threadIdx.x * d, *sn = s_nobs + threadIdx.x * d, *sa = s_act + threadIdx.x * 6;
     int t = 0, j = 0;
-    float rew = 0.f, dn = 0.f;
+    rew = 0.f;
+    dn = 0.f;
     if (slot < 0) {                                       // nothing stored (yet), or past B: zero row
         for (int k = 0; k < d; ++k) { so[k] = 0.f; sn[k] = 0.f; }
         for (int k = 0; k < 6; ++k) sa[k] = 0.f;
@@ -351,11 +356,30 @@ __global__ __launch_bounds__(BLOCK) void k_her_sample(HerK hk, int64_t B, uint64
             out.index[3 * i + 2] = slot < 0 ? 0 : j;
         }
     }
-    __syncthreads();
+}
+
+// The block's staged rows to out.obs / out.next_obs / out.action (after a barrier behind her_sample_row).
+__device__ __forceinline__ void her_flush_batch(const ctr_her_t &h, int64_t B, const ctr_her_batch_t &out,
+                                                const float *s_obs, const float *s_nobs, const float *s_act)
+{
+    const int64_t i0 = (int64_t)blockIdx.x * BLOCK;
+    const int d = h.obs_dim + 6;
     const int64_t cnt = (B - i0) < BLOCK ? (B - i0) : BLOCK;
     her_flush(out.obs + i0 * d, s_obs, cnt * d);
     her_flush(out.next_obs + i0 * d, s_nobs, cnt * d);
     her_flush(out.action + i0 * 6, s_act, cnt * 6);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_her_sample(HerK hk, int64_t B, uint64_t seed, uint64_t counter,
+                                                      ctr_her_batch_t out)
+{
+    __shared__ __attribute__((aligned(16))) float s_obs[BLOCK * HER_DMAX];
+    __shared__ __attribute__((aligned(16))) float s_nobs[BLOCK * HER_DMAX];
+    __shared__ __attribute__((aligned(16))) float s_act[BLOCK * 6];
+    float rew, dn;
+    her_sample_row(hk.h, B, seed, counter, out, s_obs, s_nobs, s_act, rew, dn);
+    __syncthreads();
+    her_flush_batch(hk.h, B, out, s_obs, s_nobs, s_act);
 }
 
 }  // namespace

@@ -17,7 +17,11 @@
 //                 the step before left in the lane's registers (ctr_rollout, at the end of the file)
 //   k_actor       the MLP actor alone, one row per lane, its blob staged into LDS (ctr_actor.inc)
 //   k_actor_load  the actor's blob packed on the device from f32 parameters, one thread per 16 B
-//                 (ctr_actor_load; ctr_actor.inc)
+//                 (ctr_actor_load, and ctr_critic_load for the critic's; ctr_actor.inc)
+//   k_critic      the MLP critic alone, the actor's code on [row, action] with a one-row output
+//                 layer (ctr_critic; ctr_critic.inc)
+//   k_her_sample_td  k_her_sample, then the target policy, the target critic and the DDPG target of
+//                 every sampled row, the two blobs taking turns in LDS (ctr_her_sample_td; ctr_critic.inc)
 //   k_collect     k_rollout with exploration noise on each action and each step recorded into the HER
 //                 store (ctr_collect, at the end of the file)
 //   k_explore     the exploration noise alone, one env per lane (ctr_explore; explore_lane, ctr_device.hpp)
@@ -3069,25 +3073,16 @@ int64_t ctr_actor_blob_bytes(const ctr_actor_t *a)
 
 int ctr_actor_pack(const ctr_actor_t *a, const float *const *W, const float *const *b, void *blob_host)
 {
-    return actor_pack(a, W, b, blob_host);
+    ActorK ak;
+    if (int r = actor_layout(a, &ak)) return r;
+    return mlp_pack(ak, "ctr_actor_pack", W, b, blob_host);
 }
 
 int ctr_actor_load(const ctr_actor_t *a, const float *const *W, const float *const *b, void *stream)
 {
     ActorK ak;
     if (int r = actor_layout(a, &ak)) return r;
-    if (!W || !b) return fail(CTR_EINVAL, "ctr_actor_load: W or b is NULL");
-    ActorSrc src = {};
-    for (int l = 0; l <= a->n_hidden; ++l) {
-        if (!W[l] || !b[l]) return fail(CTR_EINVAL, "ctr_actor_load: NULL layer among W[0..n_hidden], b[0..n_hidden]");
-        src.W[l] = W[l];
-        src.b[l] = b[l];
-    }
-    if (!a->blob) return fail(CTR_EINVAL, "actor: blob is NULL");
-    if (((uintptr_t)a->blob & 15u) != 0) return fail(CTR_EINVAL, "actor: blob must be 16-B aligned");
-    hipLaunchKernelGGL(k_actor_load, dim3(grid_for(ak.bytes / 16)), dim3(BLOCK), 0, (hipStream_t)stream, ak, src,
-                       const_cast<void *>(a->blob));
-    return hip_check("ctr_actor_load launch");
+    return mlp_load(ak, "actor", "ctr_actor_load", a->blob, W, b, stream);
 }
 
 int ctr_actor(const ctr_actor_t *a, const float *rows, int64_t n, float *actions, float *logits, void *stream)
@@ -3198,3 +3193,5 @@ int ctr_follow(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_
 }
 
 }  // extern "C"
+
+#include "ctr_critic.inc"

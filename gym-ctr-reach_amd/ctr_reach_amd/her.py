@@ -20,9 +20,11 @@ Differences from stable-baselines (documented, not hidden):
   * the relabel draws come from Philox keyed (seed, global env id, reset number, t, j), not
     numpy's global RNG, so rows match the wrapper in distribution, not draw for draw.
 """
+import ctypes
+
 import numpy as np
 
-from . import _abi
+from . import _abi, _abi_critic
 
 STRATEGIES = {"future": _abi.CTR_HER_FUTURE, "final": _abi.CTR_HER_FINAL, "episode": _abi.CTR_HER_EPISODE}
 
@@ -107,10 +109,8 @@ class HerReplayBuffer(object):
         """Stored rows (len(ReplayBuffer) of the wrapper's buffer); synchronises."""
         return int(self.rows_per_episode(self.len.clamp(min=0).cpu().numpy()).sum())
 
-    def sample(self, batch_size, seed=None, stream=None, return_index=False):
-        """ReplayBuffer.sample(batch_size) on the device: dict of obs [B, d], action [B, 6],
-        reward [B], next_obs [B, d], done [B] (d = obs_dim + 6) float32 tensors, plus index
-        [B, 3] = (slot, t, j) with ``return_index``.  Asynchronous."""
+    def _batch(self, batch_size, return_index):
+        """The output tensors of a draw of ``batch_size`` rows and their ctr_her_batch_t."""
         torch = _torch()
         B = int(batch_size)
         d = self.obs_dim + 6
@@ -126,10 +126,51 @@ class HerReplayBuffer(object):
         hb.obs, hb.action, hb.reward, hb.next_obs, hb.done, hb.index = (p(out["obs"]), p(out["action"]),
                                                                         p(out["reward"]), p(out["next_obs"]),
                                                                         p(out["done"]), p(idx))
-        s = (self.seed ^ 0x5DEECE66D) if seed is None else int(seed)
-        rc = self.lib.ctr_her_sample(self._h, B, s & 0xFFFFFFFFFFFFFFFF, self._counter, hb, _abi.stream_ptr(stream, self.venv.device.index))
-        _abi.check(rc, "ctr_her_sample")
-        self._counter += 1
         if return_index:
             out["index"] = idx
+        return B, out, hb
+
+    def _draw_seed(self, seed):
+        return ((self.seed ^ 0x5DEECE66D) if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
+
+    def sample(self, batch_size, seed=None, stream=None, return_index=False):
+        """ReplayBuffer.sample(batch_size) on the device: dict of obs [B, d], action [B, 6],
+        reward [B], next_obs [B, d], done [B] (d = obs_dim + 6) float32 tensors, plus index
+        [B, 3] = (slot, t, j) with ``return_index``.  Asynchronous."""
+        B, out, hb = self._batch(batch_size, return_index)
+        rc = self.lib.ctr_her_sample(self._h, B, self._draw_seed(seed), self._counter, hb,
+                                     _abi.stream_ptr(stream, self.venv.device.index))
+        _abi.check(rc, "ctr_her_sample")
+        self._counter += 1
+        return out
+
+    def sample_td(self, batch_size, actor, critic, gamma, seed=None, stream=None, return_index=False,
+                  return_next=False):
+        """``sample`` with the DDPG target of the drawn rows (ctr_her_sample_td): the same dict, plus
+        target [B] = reward + gamma * (1 - done) * Q'(next_obs, pi'(next_obs)) from the target policy
+        ``actor`` (an ``MlpActor``; its scale is not applied: pi' = tanh of its logits, in [-1, 1]) and
+        the target critic ``critic`` (an ``MlpCritic``), both on this buffer's device.  With
+        ``return_next`` also q_next [B] and next_action [B, 6].  One draw: the counter advances as in
+        ``sample``, and two buffers in the same state give the same rows from either.  Asynchronous."""
+        torch = _torch()
+        B, out, hb = self._batch(batch_size, return_index)
+        dev = self.venv.device
+        for net, name in ((actor, "actor"), (critic, "critic")):
+            if getattr(net, "blob", None) is None:
+                raise ValueError("sample_td: the %s must be on the device" % name)
+            if net.device.type != dev.type or (None not in (net.device.index, dev.index)
+                                               and net.device.index != dev.index):
+                raise ValueError("sample_td: the %s is on %s, the buffer on %s" % (name, net.device, dev))
+        out["target"] = torch.empty(B, dtype=torch.float32, device=dev)
+        if return_next:
+            out["q_next"] = torch.empty(B, dtype=torch.float32, device=dev)
+            out["next_action"] = torch.empty((B, 6), dtype=torch.float32, device=dev)
+        td = _abi_critic.CtrHerTd()
+        td.actor, td.critic, td.gamma = ctypes.pointer(actor._struct), ctypes.pointer(critic._struct), float(gamma)
+        td.target, td.q_next, td.next_action = (_abi.ptr(out["target"]), _abi.ptr(out.get("q_next")),
+                                                _abi.ptr(out.get("next_action")))
+        rc = self.lib.ctr_her_sample_td(self._h, B, self._draw_seed(seed), self._counter, hb, td,
+                                        _abi.stream_ptr(stream, self.venv.device.index))
+        _abi.check(rc, "ctr_her_sample_td")
+        self._counter += 1
         return out

@@ -9,12 +9,15 @@ reference's stable-baselines DDPG ``MlpPolicy`` actor on HERGoalEnvWrapper's fla
 
 ``MlpActor.emulate`` is the CPU reference of the actor's arithmetic (numpy, no GPU, no library).
 
+``MlpCritic`` is the Q-network on the same kernels (ctr_critic; ``HerReplayBuffer.sample_td`` runs a
+target policy and a target critic on every sampled row and returns the DDPG target with the batch).
+
 ``ExploreNoise`` is the exploration noise of the reference's DDPG + HER training on such an actor's
 actions (ctr_explore / ctr_collect), with its own numpy restatement.
 """
 import numpy as np
 
-from . import _abi
+from . import _abi, _abi_critic
 
 
 def bf16_round(x):
@@ -25,7 +28,163 @@ def bf16_round(x):
     return np.where(np.isnan(x), np.float32(np.nan), r).astype(np.float32)
 
 
-class MlpActor(object):
+class _Mlp(object):
+    """What the actor and the critic share: the shape checks, the packed device blob and its two
+    packers (host: ctr_*_pack, device: ctr_*_load), and the hidden layers of the emulation."""
+
+    NAME = None                 # "actor" / "critic": the messages, and ctr_<NAME>_pack / _load / _blob_bytes
+    IN_DIMS = None              # the two row lengths
+    OUT = None                  # rows of the output layer
+    TANH = None                 # whether the nn.Sequential ends with nn.Tanh
+
+    def _init_layers(self, layers, struct):
+        ws, bs = [], []
+        for W, b in layers:
+            ws.append(np.ascontiguousarray(_to_numpy(W), dtype=np.float32))
+            bs.append(np.ascontiguousarray(_to_numpy(b), dtype=np.float32).reshape(-1))
+        if not 2 <= len(ws) <= _abi.CTR_ACTOR_MAX_HIDDEN + 1:
+            raise ValueError("%s has 1..%d hidden layers and an output layer"
+                             % ("an actor" if self.NAME == "actor" else "a critic", _abi.CTR_ACTOR_MAX_HIDDEN))
+        for l, (W, b) in enumerate(zip(ws, bs)):
+            if W.ndim != 2 or b.shape != (W.shape[0],):
+                raise ValueError("layer %d: W must be [out, in] and b [out]" % l)
+            if l and W.shape[1] != ws[l - 1].shape[0]:
+                raise ValueError("layer %d takes %d inputs, layer %d gives %d" % (l, W.shape[1], l - 1, ws[l - 1].shape[0]))
+        if ws[0].shape[1] not in self.IN_DIMS:
+            raise ValueError(self._IN_MSG)
+        if ws[-1].shape[0] != self.OUT:
+            raise ValueError(self._OUT_MSG)
+        for W in ws[:-1]:
+            if W.shape[0] % 32 or not 32 <= W.shape[0] <= _abi.CTR_ACTOR_MAX_WIDTH:
+                raise ValueError("hidden widths must be multiples of 32 in 32..%d" % _abi.CTR_ACTOR_MAX_WIDTH)
+        self.weights, self.biases = ws, bs
+        self.in_dim = ws[0].shape[1]
+        self.hidden = [W.shape[0] for W in ws[:-1]]
+        self.device = None
+        self.blob = None
+        self._sources = None            # load_'s device tensors (the blob was packed from them)
+        self._struct = s = struct
+        s.in_dim, s.n_hidden = self.in_dim, len(self.hidden)
+        for l, w in enumerate(self.hidden):
+            s.width[l] = w
+
+    @property
+    def _A(self):
+        return "the " + self.NAME
+
+    def _fn(self, what):
+        return "ctr_%s_%s" % (self.NAME, what)
+
+    def load_(self, layers, stream=None, keep_host=False):
+        """Refresh the device blob in place from device-resident parameters (ctr_actor_load /
+        ctr_critic_load): one launch on ``stream`` (default: the current stream), ordered like any
+        other launch there; no allocation, no copy to the host and no synchronisation, so it can be
+        captured into a graph (a replay packs whatever the parameters hold then).  ``layers``:
+        [(W, b), ...] torch tensors or an ``nn.Sequential`` as ``from_torch`` takes; every tensor on
+        the network's device, float32, contiguous and of its shapes, or ValueError is raised and the
+        blob stays (nothing is converted: a hidden copy would be a temporary the launch outlives).
+        The tensors stay referenced until the next ``load_``.
+
+        The host copies (``weights``, ``biases``, ``packed``) would go stale: they are dropped, and
+        ``emulate`` / ``reference`` raise until a load with ``keep_host=True``, which copies the
+        sources back to the host and therefore SYNCHRONISES (not for a captured graph).  Returns
+        self."""
+        import torch
+        if self.blob is None:
+            raise RuntimeError("%s is on the host (%s(..., device=None)): nothing to load into"
+                               % (self._A, type(self).__name__))
+        if isinstance(layers, torch.nn.Module):
+            layers = _sequential_layers(layers, self.TANH, self.NAME)
+        layers = [tuple(pair) for pair in layers]
+        dims = [self.in_dim] + self.hidden + [self.OUT]
+        if len(layers) != len(dims) - 1 or any(len(pair) != 2 for pair in layers):
+            raise ValueError("%s has %d layers of (W, b)" % (self._A, len(dims) - 1))
+        src = []
+        for l, (W, b) in enumerate(layers):
+            pair = []
+            for name, t, shape in (("W", W, (dims[l + 1], dims[l])), ("b", b, (dims[l + 1],))):
+                what = "layer %d: %s" % (l, name)
+                if not isinstance(t, torch.Tensor):
+                    raise ValueError(what + " must be a torch tensor")
+                if t.device.type != self.device.type or (self.device.index is not None
+                                                         and t.device.index != self.device.index):
+                    raise ValueError("%s is on %s, %s on %s" % (what, t.device, self._A, self.device))
+                if t.dtype != torch.float32:
+                    raise ValueError("%s must be float32, not %s" % (what, t.dtype))
+                if tuple(t.shape) != shape:
+                    raise ValueError("%s must be %s, not %s" % (what, list(shape), list(t.shape)))
+                if not t.is_contiguous():
+                    raise ValueError(what + " must be contiguous")
+                pair.append(t.detach())
+            src.append(tuple(pair))
+        n = len(src)
+        W = (_abi._P * n)(*[w.data_ptr() for w, _ in src])
+        b = (_abi._P * n)(*[v.data_ptr() for _, v in src])
+        rc = getattr(_abi.load(), self._fn("load"))(self._struct, W, b, _abi.stream_ptr(stream, self.device.index))
+        _abi.check(rc, self._fn("load"))
+        self._sources = src
+        self.weights = self.biases = self.packed = None
+        if keep_host:
+            if stream is not None:
+                stream.synchronize()
+            self.weights = [np.ascontiguousarray(_to_numpy(w), dtype=np.float32) for w, _ in src]
+            self.biases = [np.ascontiguousarray(_to_numpy(v), dtype=np.float32) for _, v in src]
+            self.packed = self._pack_host()
+        return self
+
+    def _pack_host(self):
+        """ctr_actor_pack / ctr_critic_pack of the host copies -> the blob's bytes (numpy uint8)."""
+        lib = _abi.load()
+        nb = int(getattr(lib, self._fn("blob_bytes"))(self._struct))
+        if nb < 0:
+            raise _abi.CtrError(self._fn("blob_bytes") + ": " + lib.ctr_last_error().decode())
+        host = np.zeros(nb, dtype=np.uint8)
+        n = len(self.weights)
+        W = (_abi._P * n)(*[w.ctypes.data for w in self.weights])
+        b = (_abi._P * n)(*[v.ctypes.data for v in self.biases])
+        _abi.check(getattr(lib, self._fn("pack"))(self._struct, W, b, host.ctypes.data), self._fn("pack"))
+        return host
+
+    def _upload(self, device):
+        import torch
+        self.packed = host = self._pack_host()
+        self.device = torch.device(device)
+        self.blob = torch.from_numpy(host).to(self.device)
+        if self.blob.data_ptr() % 16:
+            raise RuntimeError(self.NAME + " blob not 16-B aligned")
+        self._struct.blob = self.blob.data_ptr()
+
+    def _emulate_output(self, x):
+        """The shared arithmetic (include/ctr_reach_amd.h) in numpy float64 with the kernel's bf16
+        roundings: x [n, in_dim] float32 -> the output layer's result [n, OUT] float64; the bf16
+        activations of every hidden layer in ``self.last_hidden``."""
+        hi = bf16_round(x)
+        lo = bf16_round(x - hi)
+        Wq = [bf16_round(W).astype(np.float64) for W in self.weights]
+        z = hi.astype(np.float64) @ Wq[0].T + lo.astype(np.float64) @ Wq[0].T
+        self.last_hidden = []
+        for l in range(len(self.hidden)):
+            z = (z.astype(np.float32) + self.biases[l]).astype(np.float32)      # f32 result + f32 bias
+            h = bf16_round(np.where(z > 0, z, np.float32(0)))
+            self.last_hidden.append(h)
+            z = h.astype(np.float64) @ Wq[l + 1].T
+        return z + self.biases[-1].astype(np.float64)
+
+    def _reference_output(self, x):
+        """The plain float64 MLP (no bf16 anywhere) up to the output layer's result."""
+        z = x
+        for l, (W, b) in enumerate(zip(self.weights, self.biases)):
+            z = z @ W.astype(np.float64).T + b.astype(np.float64)
+            if l < len(self.hidden):
+                z = np.maximum(z, 0.0)
+        return z
+
+    def _need_host(self):
+        if self.weights is None:
+            raise RuntimeError("the host copy of the weights was dropped by load_; load with keep_host=True")
+
+
+class MlpActor(_Mlp):
     """``layers``: [(W, b), ...] numpy arrays or torch tensors in torch's [out, in] convention, 1..3
     hidden layers (widths multiples of 32, at most 256) and the 6-row output layer; the first
     layer takes the flat row of obs_dim + 6 = 19 or 20 floats.  ``scale``: the action space's high
@@ -43,41 +202,17 @@ class MlpActor(object):
             optimiser.step()
             actor.load_(policy)                   # ctr_actor_load: the blob now holds the new weights"""
 
+    NAME, IN_DIMS, OUT, TANH = "actor", (19, 20), 6, True
+    _IN_MSG = "the first layer takes the flat row of obs_dim + 6 = 19 or 20 floats"
+    _OUT_MSG = "the output layer has 6 rows (the actions)"
+
     def __init__(self, layers, scale, device=None):
-        ws, bs = [], []
-        for W, b in layers:
-            ws.append(np.ascontiguousarray(_to_numpy(W), dtype=np.float32))
-            bs.append(np.ascontiguousarray(_to_numpy(b), dtype=np.float32).reshape(-1))
-        if not 2 <= len(ws) <= _abi.CTR_ACTOR_MAX_HIDDEN + 1:
-            raise ValueError("an actor has 1..%d hidden layers and an output layer" % _abi.CTR_ACTOR_MAX_HIDDEN)
-        for l, (W, b) in enumerate(zip(ws, bs)):
-            if W.ndim != 2 or b.shape != (W.shape[0],):
-                raise ValueError("layer %d: W must be [out, in] and b [out]" % l)
-            if l and W.shape[1] != ws[l - 1].shape[0]:
-                raise ValueError("layer %d takes %d inputs, layer %d gives %d" % (l, W.shape[1], l - 1, ws[l - 1].shape[0]))
-        if ws[0].shape[1] not in (19, 20):
-            raise ValueError("the first layer takes the flat row of obs_dim + 6 = 19 or 20 floats")
-        if ws[-1].shape[0] != 6:
-            raise ValueError("the output layer has 6 rows (the actions)")
-        for W in ws[:-1]:
-            if W.shape[0] % 32 or not 32 <= W.shape[0] <= _abi.CTR_ACTOR_MAX_WIDTH:
-                raise ValueError("hidden widths must be multiples of 32 in 32..%d" % _abi.CTR_ACTOR_MAX_WIDTH)
-        self.weights, self.biases = ws, bs
-        self.in_dim = ws[0].shape[1]
-        self.hidden = [W.shape[0] for W in ws[:-1]]
+        self._init_layers(layers, _abi.CtrActor())
         self.scale = np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
         if self.scale.shape != (6,) or not np.isfinite(self.scale).all():
             raise ValueError("scale must be 6 finite floats")
-        self.device = None
-        self.blob = None
-        self._sources = None            # load_'s device tensors (the blob was packed from them)
-        self._struct = _abi.CtrActor()
-        s = self._struct
-        s.in_dim, s.n_hidden = self.in_dim, len(self.hidden)
-        for l, w in enumerate(self.hidden):
-            s.width[l] = w
         for i in range(6):
-            s.scale[i] = float(self.scale[i])
+            self._struct.scale[i] = float(self.scale[i])
         if device is not None:
             self._upload(device)
 
@@ -86,84 +221,6 @@ class MlpActor(object):
         """From an ``nn.Sequential`` of Linear, ReLU, ..., Linear, Tanh."""
         return cls(_sequential_layers(seq), scale, device)
 
-    def load_(self, layers, stream=None, keep_host=False):
-        """Refresh the device blob in place from device-resident parameters (ctr_actor_load): one
-        launch on ``stream`` (default: the current stream), ordered like any other launch there; no
-        allocation, no copy to the host and no synchronisation, so it can be captured into a graph
-        (a replay packs whatever the parameters hold then).  ``layers``: [(W, b), ...] torch tensors
-        or an ``nn.Sequential`` as ``from_torch`` takes; every tensor on the actor's device,
-        float32, contiguous and of the actor's shapes, or ValueError is raised and the blob stays
-        (nothing is converted: a hidden copy would be a temporary the launch outlives).  The
-        tensors stay referenced by the actor until the next ``load_``.
-
-        The host copies (``weights``, ``biases``, ``packed``) would go stale: they are dropped, and
-        ``emulate`` / ``reference`` raise until a load with ``keep_host=True``, which copies the
-        sources back to the host and therefore SYNCHRONISES (not for a captured graph).  Returns
-        the actor."""
-        import torch
-        if self.blob is None:
-            raise RuntimeError("the actor is on the host (MlpActor(..., device=None)): nothing to load into")
-        if isinstance(layers, torch.nn.Module):
-            layers = _sequential_layers(layers)
-        layers = [tuple(pair) for pair in layers]
-        dims = [self.in_dim] + self.hidden + [6]
-        if len(layers) != len(dims) - 1 or any(len(pair) != 2 for pair in layers):
-            raise ValueError("the actor has %d layers of (W, b)" % (len(dims) - 1))
-        src = []
-        for l, (W, b) in enumerate(layers):
-            pair = []
-            for name, t, shape in (("W", W, (dims[l + 1], dims[l])), ("b", b, (dims[l + 1],))):
-                what = "layer %d: %s" % (l, name)
-                if not isinstance(t, torch.Tensor):
-                    raise ValueError(what + " must be a torch tensor")
-                if t.device.type != self.device.type or (self.device.index is not None
-                                                         and t.device.index != self.device.index):
-                    raise ValueError("%s is on %s, the actor on %s" % (what, t.device, self.device))
-                if t.dtype != torch.float32:
-                    raise ValueError("%s must be float32, not %s" % (what, t.dtype))
-                if tuple(t.shape) != shape:
-                    raise ValueError("%s must be %s, not %s" % (what, list(shape), list(t.shape)))
-                if not t.is_contiguous():
-                    raise ValueError(what + " must be contiguous")
-                pair.append(t.detach())
-            src.append(tuple(pair))
-        n = len(src)
-        W = (_abi._P * n)(*[w.data_ptr() for w, _ in src])
-        b = (_abi._P * n)(*[v.data_ptr() for _, v in src])
-        rc = _abi.load().ctr_actor_load(self._struct, W, b, _abi.stream_ptr(stream, self.device.index))
-        _abi.check(rc, "ctr_actor_load")
-        self._sources = src
-        self.weights = self.biases = self.packed = None
-        if keep_host:
-            if stream is not None:
-                stream.synchronize()
-            self.weights = [np.ascontiguousarray(_to_numpy(w), dtype=np.float32) for w, _ in src]
-            self.biases = [np.ascontiguousarray(_to_numpy(v), dtype=np.float32) for _, v in src]
-            self.packed = self._pack_host()
-        return self
-
-    def _pack_host(self):
-        """ctr_actor_pack of the host copies -> the blob's bytes (numpy uint8)."""
-        lib = _abi.load()
-        nb = int(lib.ctr_actor_blob_bytes(self._struct))
-        if nb < 0:
-            raise _abi.CtrError("ctr_actor_blob_bytes: " + lib.ctr_last_error().decode())
-        host = np.zeros(nb, dtype=np.uint8)
-        n = len(self.weights)
-        W = (_abi._P * n)(*[w.ctypes.data for w in self.weights])
-        b = (_abi._P * n)(*[v.ctypes.data for v in self.biases])
-        _abi.check(lib.ctr_actor_pack(self._struct, W, b, host.ctypes.data), "ctr_actor_pack")
-        return host
-
-    def _upload(self, device):
-        import torch
-        self.packed = host = self._pack_host()
-        self.device = torch.device(device)
-        self.blob = torch.from_numpy(host).to(self.device)
-        if self.blob.data_ptr() % 16:
-            raise RuntimeError("actor blob not 16-B aligned")
-        self._struct.blob = self.blob.data_ptr()
-
     def emulate(self, rows):
         """The actor's arithmetic (include/ctr_reach_amd.h) in numpy float64 with the kernel's bf16
         roundings: rows [n, in_dim] -> (actions [n, 6], logits [n, 6]) float64.  Also returns the
@@ -171,32 +228,14 @@ class MlpActor(object):
         self._need_host()
         x = np.asarray(rows, dtype=np.float32).reshape(-1, self.in_dim)
         with np.errstate(invalid="ignore", over="ignore"):
-            hi = bf16_round(x)
-            lo = bf16_round(x - hi)
-            Wq = [bf16_round(W).astype(np.float64) for W in self.weights]
-            z = hi.astype(np.float64) @ Wq[0].T + lo.astype(np.float64) @ Wq[0].T
-            self.last_hidden = []
-            for l in range(len(self.hidden)):
-                z = (z.astype(np.float32) + self.biases[l]).astype(np.float32)      # f32 result + f32 bias
-                h = bf16_round(np.where(z > 0, z, np.float32(0)))
-                self.last_hidden.append(h)
-                z = h.astype(np.float64) @ Wq[l + 1].T
-            y = z + self.biases[-1].astype(np.float64)
+            y = self._emulate_output(x)
             return self.scale.astype(np.float64) * np.tanh(y), y
 
     def reference(self, rows):
         """The plain float64 MLP (no bf16 anywhere): actions [n, 6]."""
         self._need_host()
-        z = np.asarray(rows, dtype=np.float64).reshape(-1, self.in_dim)
-        for l, (W, b) in enumerate(zip(self.weights, self.biases)):
-            z = z @ W.astype(np.float64).T + b.astype(np.float64)
-            if l < len(self.hidden):
-                z = np.maximum(z, 0.0)
+        z = self._reference_output(np.asarray(rows, dtype=np.float64).reshape(-1, self.in_dim))
         return self.scale.astype(np.float64) * np.tanh(z)
-
-    def _need_host(self):
-        if self.weights is None:
-            raise RuntimeError("the host copy of the weights was dropped by load_; load with keep_host=True")
 
     def __call__(self, rows, logits=False, stream=None):
         """ctr_actor: rows [n, in_dim] float32 device tensor -> actions [n, 6] (and the pre-tanh
@@ -214,6 +253,73 @@ class MlpActor(object):
                                    _abi.stream_ptr(stream, self.device.index))
         _abi.check(rc, "ctr_actor")
         return (act, lg) if logits else act
+
+
+class MlpCritic(_Mlp):
+    """The Q-network of the reference's DDPG on the device (ctr_critic / ctr_her_sample_td).
+    ``layers``: [(W, b), ...] as ``MlpActor`` takes them, 1..3 hidden layers (widths multiples of
+    32, at most 256) and the 1-row output layer; the first layer takes [row, action]: the flat row
+    and the six actions in the normalised box [-1, 1], obs_dim + 12 = 25 or 26 floats.  ``device``
+    None keeps the critic on the host (``emulate`` only).
+
+        critic_targ = MlpCritic.from_torch(critic_targ_net, "cuda")
+        q = critic_targ(rows, actions / scale)                  # one ctr_critic launch
+        batch = her.sample_td(256, actor_targ, critic_targ, 0.98)   # the batch and its DDPG target
+        critic_targ.load_(critic_targ_net)                      # after the Polyak update: ctr_critic_load
+
+    ``emulate`` is the CPU reference of the arithmetic (numpy, no GPU, no library)."""
+
+    NAME, IN_DIMS, OUT, TANH = "critic", (25, 26), 1, False
+    _IN_MSG = "the first layer takes [row, action]: obs_dim + 12 = 25 or 26 floats"
+    _OUT_MSG = "the output layer has 1 row (Q)"
+
+    def __init__(self, layers, device=None):
+        self._init_layers(layers, _abi_critic.CtrCritic())
+        if device is not None:
+            self._upload(device)
+
+    @classmethod
+    def from_torch(cls, seq, device=None):
+        """From an ``nn.Sequential`` of Linear, ReLU, ..., Linear (no Tanh, one output)."""
+        return cls(_sequential_layers(seq, False, "critic"), device)
+
+    def _input(self, rows, actions, dtype):
+        r = np.asarray(rows, dtype=dtype).reshape(-1, self.in_dim - 6)
+        a = np.asarray(actions, dtype=dtype).reshape(-1, 6)
+        if r.shape[0] != a.shape[0]:
+            raise ValueError("rows and actions differ in length")
+        return np.concatenate([r, a], axis=1)
+
+    def emulate(self, rows, actions):
+        """The critic's arithmetic (include/ctr_reach_amd.h) in numpy float64 with the kernel's bf16
+        roundings: rows [n, in_dim - 6], actions [n, 6] -> q [n] float64.  The bf16 activations of
+        every hidden layer are left in ``self.last_hidden``."""
+        self._need_host()
+        with np.errstate(invalid="ignore", over="ignore"):
+            return self._emulate_output(self._input(rows, actions, np.float32))[:, 0]
+
+    def reference(self, rows, actions):
+        """The plain float64 MLP (no bf16 anywhere): q [n]."""
+        self._need_host()
+        return self._reference_output(self._input(rows, actions, np.float64))[:, 0]
+
+    def __call__(self, rows, actions, stream=None):
+        """ctr_critic: rows [n, in_dim - 6] and actions [n, 6] float32 device tensors -> q [n]."""
+        import torch
+        if self.blob is None:
+            raise RuntimeError("the critic is on the host (MlpCritic(..., device=None))")
+        rows = rows.to(device=self.device, dtype=torch.float32).contiguous()
+        actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        if rows.dim() != 2 or rows.shape[1] != self.in_dim - 6:
+            raise ValueError("rows must be [n, %d]" % (self.in_dim - 6))
+        n = rows.shape[0]
+        if tuple(actions.shape) != (n, 6):
+            raise ValueError("actions must be [%d, 6]" % n)
+        q = torch.empty(n, dtype=torch.float32, device=self.device)
+        rc = _abi.load().ctr_critic(self._struct, _abi.ptr(rows), _abi.ptr(actions), n, _abi.ptr(q),
+                                    _abi.stream_ptr(stream, self.device.index))
+        _abi.check(rc, "ctr_critic")
+        return q
 
 
 def philox4x32(counter, key):
@@ -304,22 +410,27 @@ class ExploreNoise(object):
         return np.where(rnd[:, None], uniform.astype(np.float64), gauss)
 
 
-def _sequential_layers(seq):
-    """[(W, b), ...] (detached) of an ``nn.Sequential`` of Linear, ReLU, ..., Linear, Tanh."""
+def _sequential_layers(seq, tanh=True, name="actor"):
+    """[(W, b), ...] (detached) of an ``nn.Sequential`` of Linear, ReLU, ..., Linear, then Tanh (the
+    actor) or nothing (the critic)."""
     import torch.nn as nn
     mods = list(seq)
-    if not mods or not isinstance(mods[-1], nn.Tanh):
-        raise ValueError("the actor ends with nn.Tanh")
+    if tanh:
+        if not mods or not isinstance(mods[-1], nn.Tanh):
+            raise ValueError("the actor ends with nn.Tanh")
+        mods = mods[:-1]
+    elif not mods or not isinstance(mods[-1], nn.Linear):
+        raise ValueError("the %s ends with its output nn.Linear (no activation after it)" % name)
     layers = []
-    for i, m in enumerate(mods[:-1]):
+    for i, m in enumerate(mods):
         if i % 2 == 0:
             if not isinstance(m, nn.Linear) or m.bias is None:
                 raise ValueError("module %d must be an nn.Linear with a bias" % i)
             layers.append((m.weight.detach(), m.bias.detach()))
         elif not isinstance(m, nn.ReLU):
             raise ValueError("module %d must be an nn.ReLU" % i)
-    if len(mods) % 2:
-        raise ValueError("expected Linear, ReLU, ..., Linear, Tanh")
+    if len(mods) % 2 == 0:
+        raise ValueError("expected Linear, ReLU, ..., Linear" + (", Tanh" if tanh else ""))
     return layers
 
 

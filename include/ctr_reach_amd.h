@@ -35,6 +35,11 @@
  *                       ctr_rollout together with the env.step calls of those loops
  *   ctr_actor_load      the learner's parameters into that actor after a policy update of the
  *                       training pipeline (stable-baselines shares them inside one TensorFlow graph)
+ *   ctr_critic / ctr_her_sample_td
+ *                       the target-Q part of stable-baselines DDPG's _setup_target_network_updates /
+ *                       _train_step: r + gamma (1 - done) Q'(s', pi'(s')) from the target networks,
+ *                       ctr_her_sample_td together with the replay draw that feeds it
+ *                       (ctr_critic_load: the Polyak-updated target parameters into the critic's blob)
  *   ctr_explore / ctr_collect
  *                       the data collection of the reference's training pipeline, stable-baselines
  *                       DDPG under HER: NormalActionNoise clipped to the action box and
@@ -670,6 +675,66 @@ typedef struct ctr_follow_t {
 int ctr_follow(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *actor,
                const ctr_follow_t *follow, int32_t k, const ctr_step_out_t *out,
                float *actions /* [k][n][6] or NULL */, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * MLP critic and the TD target (entry points added within ABI 17: no existing entry point or struct
+ * changes, so the number stays; a caller that needs them looks the symbols up).  The Q-network of
+ * the reference's stable-baselines DDPG on x = [row, a] (in_dim = obs_dim + 12 floats): row is
+ * HERGoalEnvWrapper's flat row [observation, achieved_goal, desired_goal] (the layout of
+ * ctr_her_batch_t.obs) and a the six actions in the normalised box [-1, 1], as that critic sees
+ * them (the caller divides by the action scale; no entry point here applies one).  The arithmetic
+ * is the actor's, with a one-row output layer and no tanh:
+ *     x_hi = bf16(x);  x_lo = bf16(x - float(x_hi))        (round to nearest even; x - x_hi in f32)
+ *     h1   = bf16(relu(W1 x_hi + W1 x_lo + b1))            (bf16 weights, f32 accumulation, f32 bias)
+ *     hl   = bf16(relu(Wl h(l-1) + bl))                    the further hidden layers
+ *     q    = Wout hL + bout                                f32
+ * A row's q depends on that row and the weights only.  The blob's layout is exactly the actor's
+ * ("MLP actor" above): the same fragment order, layer 0 with 2 k-steps over the in_dim inputs
+ * padded to 32, the biases behind the fragments, each padded to whole 32-row tiles; the output
+ * layer has 1 row where the actor has 6.  The byte limit is CTR_ACTOR_MAX_BYTES. */
+typedef struct ctr_critic_t {
+    int32_t in_dim;                       /* obs_dim + 12: 25 or 26                        */
+    int32_t n_hidden;                     /* 1..CTR_ACTOR_MAX_HIDDEN                       */
+    int32_t width[CTR_ACTOR_MAX_HIDDEN];  /* multiples of 32, <= CTR_ACTOR_MAX_WIDTH       */
+    int32_t pad;
+    const void *blob;                     /* device, 16-B aligned, ctr_critic_blob_bytes() */
+} ctr_critic_t;
+/* As ctr_actor_blob_bytes, ctr_actor_pack (host only) and ctr_actor_load (one launch that writes
+ * every byte of c->blob, padding included) are for the actor; the last layer is the 1-row output
+ * layer.  ctr_critic_blob_bytes and ctr_critic_pack do not read blob. */
+int64_t ctr_critic_blob_bytes(const ctr_critic_t *c);
+int ctr_critic_pack(const ctr_critic_t *c, const float *const *W, const float *const *b, void *blob_host);
+int ctr_critic_load(const ctr_critic_t *c, const float *const *W, const float *const *b, void *stream);
+/* rows [n][in_dim - 6] f32, actions [n][6] f32 -> q [n] f32.  (device)  Refused (CTR_EINVAL, before
+ * any HIP call): a refused shape, a NULL or misaligned blob, n out of range, a NULL array where
+ * n > 0.  n = 0 is a no-op. */
+int ctr_critic(const ctr_critic_t *c, const float *rows, const float *actions, int64_t n, float *q, void *stream);
+
+/* ctr_her_sample that also hands the learner the DDPG target of the rows it drew.  It writes
+ * everything ctr_her_sample writes for the same (her, batch_size, seed, counter), bit for bit, and
+ * in the same launch, for each sampled row,
+ *     a'     = tanhf(y),  y = the target policy's logits on the f32 row stored to out->next_obs
+ *                         (ctr_actor's arithmetic; actor->scale is not read)
+ *     q      = critic([next_obs row, a'])                  (ctr_critic's arithmetic)
+ *     target = done != 0 ? reward : (gamma * q) + reward   (two f32 roundings, no fused multiply-add)
+ * A zero row (empty store: index slot -1) goes through the networks like any other row.  The two
+ * blobs take turns in one LDS region beside the sampler's row staging, so every supported actor
+ * works with every supported critic.  Three launches (the sampler's two scans, then this kernel);
+ * stream-ordered, nothing allocated, nothing read back.
+ * Refused (CTR_EINVAL, before any HIP call): whatever ctr_her_sample refuses; a NULL td or
+ * td->target; a refused actor or critic; actor->in_dim != her->obs_dim + 6; critic->in_dim !=
+ * her->obs_dim + 12; a non-finite gamma.  batch_size = 0 is a no-op. */
+typedef struct ctr_her_td_t {
+    const ctr_actor_t  *actor;    /* target policy; its scale is not read                  */
+    const ctr_critic_t *critic;   /* target critic                                         */
+    float   gamma;                /* finite                                                */
+    int32_t pad;
+    float  *target;               /* [B] device, required                                  */
+    float  *q_next;               /* [B] or NULL: Q'(s', pi'(s'))                          */
+    float  *next_action;          /* [B][6] or NULL: pi'(s') = tanhf(y), in [-1, 1]        */
+} ctr_her_td_t;
+int ctr_her_sample_td(const ctr_her_t *her, int64_t batch_size, uint64_t seed, uint64_t counter,
+                      const ctr_her_batch_t *out, const ctr_her_td_t *td, void *stream);
 
 /* CtrReachEnv.reset for the environments with mask[i] != 0 (mask NULL = all).
  * goal [n][3] or NULL (sample a goal), system [n] or NULL (sample uniformly).
