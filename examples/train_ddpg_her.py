@@ -30,9 +30,15 @@ target networks stay the owners of the float32 parameters; the blobs are their b
 targets then come from bf16 weights and activations (ctr_reach_amd/policy.py, ``emulate``) instead
 of torch's float32 arithmetic.
 
+With ``--device-polyak`` (``main(..., device_polyak=True)``, which implies the device targets) the
+Polyak update moves to the device as well: the per-parameter ``lerp_`` loop and the two ``load_``
+become one ``polyak_`` call, one launch that updates the float32 target parameters in place and
+repacks both blobs from them.  The torch target modules still own those parameters, so their
+``state_dict()`` is what it was.
+
 usage: python examples/train_ddpg_her.py [--num-envs N] [--iterations I] [--steps-per-iter S]
            [--batch-size B] [--updates-per-iter U] [--hidden 64,64] [--seed 0] [--device cuda]
-           [--device-targets]"""
+           [--device-targets] [--device-polyak]"""
 import argparse
 import os
 import sys
@@ -44,7 +50,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-ctr-reach_amd"))
 from ctr_reach_amd import CtrReachVecEnv  # noqa: E402
-from ctr_reach_amd.policy import ExploreNoise, MlpActor, MlpCritic  # noqa: E402
+from ctr_reach_amd.policy import ExploreNoise, MlpActor, MlpCritic, polyak_  # noqa: E402
 
 GAMMA, TAU, ACTOR_LR, CRITIC_LR = 0.99, 0.001, 1e-4, 1e-3
 N_SAMPLED_GOAL, STRATEGY = 4, "future"
@@ -63,8 +69,9 @@ def mlp(n_in, hidden, n_out, tanh):
 
 
 def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, updates_per_iter=40, hidden=(64, 64), seed=0,
-         device="cuda", device_targets=False):
+         device="cuda", device_targets=False, device_polyak=False):
     device = torch.device(device)
+    device_targets = device_targets or device_polyak
     torch.manual_seed(seed)
     venv = CtrReachVecEnv(num_envs, device=device, seed=seed)
     her = venv.enable_her(n_sampled_goal=N_SAMPLED_GOAL, goal_selection_strategy=STRATEGY)
@@ -113,13 +120,16 @@ def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, update
             policy_opt.zero_grad(set_to_none=True)
             policy_loss.backward()         # (the critic's gradients from this pass are dropped by its zero_grad)
             policy_opt.step()
-            with torch.no_grad():
-                for net, targ in ((policy, policy_targ), (critic, critic_targ)):
-                    for p, pt in zip(net.parameters(), targ.parameters()):
-                        pt.lerp_(p, TAU)
-            if device_targets:
-                actor_targ.load_(policy_targ)
-                critic_targ_dev.load_(critic_targ)
+            if device_polyak:                                                # the update and both blobs: one launch
+                polyak_([(actor_targ, policy, policy_targ), (critic_targ_dev, critic, critic_targ)], TAU)
+            else:
+                with torch.no_grad():
+                    for net, targ in ((policy, policy_targ), (critic, critic_targ)):
+                        for p, pt in zip(net.parameters(), targ.parameters()):
+                            pt.lerp_(p, TAU)
+                if device_targets:
+                    actor_targ.load_(policy_targ)
+                    critic_targ_dev.load_(critic_targ)
             critic_sum += critic_loss.detach()
             policy_sum += policy_loss.detach()
         actor.load_(policy)
@@ -141,9 +151,12 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--device-targets", action="store_true", help="the DDPG target from her.sample_td (bf16 target networks)")
+    ap.add_argument("--device-polyak", action="store_true",
+                    help="the Polyak update and both blob refreshes in one polyak_ launch (implies --device-targets)")
     args = ap.parse_args()
     out = main(args.num_envs, args.iterations, args.steps_per_iter, args.batch_size, args.updates_per_iter,
-               tuple(int(w) for w in args.hidden.split(",")), args.seed, args.device, args.device_targets)
+               tuple(int(w) for w in args.hidden.split(",")), args.seed, args.device, args.device_targets,
+               args.device_polyak)
     for it, (c, p) in enumerate(out["losses"]):
         print("iteration %3d: critic loss %.4g, policy loss %.4g" % (it, c, p))
     stats = out["rollout_stats"]

@@ -206,69 +206,105 @@ struct ActorSrc {
 
 typedef float actor_f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // a parameter tensor may start at any float
 
+// Item i (16 B) of a blob and the elements of its layer's parameter tensors that it holds: the one
+// place that knows the packer's thread-to-element mapping on the device (k_actor_load, and k_polyak
+// in ctr_polyak.inc, which also writes those elements).  A bias item holds b[e .. e + 3] below
+// rows; a weight item holds, of row `row` (when below rows), the columns actor_k_of(l, S, h, 0..7)
+// below cols.
+struct ActorItem {
+    bool bias;
+    int l, rows, cols;                 // the layer, and its real rows and columns
+    int e;                             // bias: the first of its four floats
+    int row, S, h;                     // weights: the fragment's row, k-step and lane half
+};
+
+__device__ __forceinline__ ActorItem actor_item(const ActorK &ak, uint32_t i)
+{
+    ActorItem it = {};
+    const uint32_t byte = 16 * i;
+    it.bias = byte >= ak.b_off[0];
+    // the item's layer and its place in it; the arrays by constant index (they are kernel arguments)
+    uint32_t off = 0;
+    #pragma unroll
+    for (int m = 0; m < ACTOR_LAYERS; ++m) {
+        const uint32_t start = it.bias ? ak.b_off[m] : ak.w_off[m];
+        if (m <= ak.n_hidden && byte >= start) {
+            it.l = m;
+            off = byte - start;
+            it.rows = m < ak.n_hidden ? 32 * ak.tiles[m] : ak.out_rows;
+            it.cols = m == 0 ? ak.in_dim : 32 * ak.tiles[m - 1];
+        }
+    }
+    if (it.bias) {
+        it.e = (int)(off / 4);
+    } else {
+        const int ksteps = it.l == 0 ? 2 : it.cols / 16;
+        const int f = (int)(off / 16), lane = f & 63, ts = f >> 6;
+        const int T = ts / ksteps;
+        it.h = lane >> 5;
+        it.S = ts - T * ksteps;
+        it.row = 32 * T + (lane & 31);
+    }
+    return it;
+}
+
+// The item's elements of one layer's tensors (p = b for a bias item, W for a weight item) as bits in
+// flight: v[0..3] the bias floats, v[0..7] the fragment's weights; what lies past the tensor is +0
+// and is not read.
+__device__ __forceinline__ void actor_item_load(const ActorItem &it, const float *p, float v[8])
+{
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = 0.f;
+    if (it.bias) {
+        // rows is 6 or 1 in the output layer, so the tail is guarded per float
+        #pragma unroll
+        for (int t = 0; t < 4; ++t)
+            if (it.e + t < it.rows) v[t] = p[it.e + t];
+    } else if (it.row < it.rows) {
+        const float *wr = p + (size_t)it.row * it.cols;
+        if (it.l == 0) {
+            // eight consecutive floats of an in_dim-float row (19 or 20; the critic's: 25 or 26)
+            #pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int k = actor_k_of(0, it.S, it.h, j);
+                if (k < it.cols) v[j] = wr[k];
+            }
+        } else {
+            // two runs of four (cols is a multiple of 32, so both lie inside the row)
+            const actor_f32x4u a0 = *reinterpret_cast<const actor_f32x4u *>(wr + actor_k_of(it.l, it.S, it.h, 0));
+            const actor_f32x4u a1 = *reinterpret_cast<const actor_f32x4u *>(wr + actor_k_of(it.l, it.S, it.h, 4));
+            #pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                v[j] = a0[j];
+                v[4 + j] = a1[j];
+            }
+        }
+    }
+}
+
+// The item's 16 B of the blob from those elements: the biases copied as bits, the weights rounded.
+__device__ __forceinline__ uint4 actor_item_pack(const ActorItem &it, const float v[8])
+{
+    uint32_t w[4];
+    #pragma unroll
+    for (int j = 0; j < 4; ++j)
+        w[j] = it.bias ? __float_as_uint(v[j])
+                       : (uint32_t)actor_bf16_bits(v[2 * j]) | ((uint32_t)actor_bf16_bits(v[2 * j + 1]) << 16);   // +0 -> 0
+    return uint4{w[0], w[1], w[2], w[3]};
+}
+
 __global__ __launch_bounds__(BLOCK) void k_actor_load(ActorK ak, ActorSrc src, void *__restrict__ blob)
 {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= ak.bytes / 16) return;
-    const uint32_t byte = 16 * i;
-    const bool bias = byte >= ak.b_off[0];
-    // the item's layer and its place in it; the arrays by constant index (they are kernel arguments)
-    int l = 0, rows = 0, cols = 0;
-    uint32_t off = 0;
-    const float *W = nullptr, *b = nullptr;
+    const ActorItem it = actor_item(ak, i);
+    const float *p = nullptr;
     #pragma unroll
-    for (int m = 0; m < ACTOR_LAYERS; ++m) {
-        const uint32_t start = bias ? ak.b_off[m] : ak.w_off[m];
-        if (m <= ak.n_hidden && byte >= start) {
-            l = m;
-            off = byte - start;
-            rows = m < ak.n_hidden ? 32 * ak.tiles[m] : ak.out_rows;
-            cols = m == 0 ? ak.in_dim : 32 * ak.tiles[m - 1];
-            W = src.W[m];
-            b = src.b[m];
-        }
-    }
-    uint4 out = {0u, 0u, 0u, 0u};
-    if (bias) {
-        // copied as bits; rows is 6 or 1 in the output layer, so the tail is guarded per float
-        const int e = (int)(off / 4);
-        const uint32_t *bb = reinterpret_cast<const uint32_t *>(b);
-        uint32_t v[4];
-        #pragma unroll
-        for (int t = 0; t < 4; ++t) v[t] = e + t < rows ? bb[e + t] : 0u;
-        out = {v[0], v[1], v[2], v[3]};
-    } else {
-        const int ksteps = l == 0 ? 2 : cols / 16;
-        const int f = (int)(off / 16), lane = f & 63, h = lane >> 5, ts = f >> 6;
-        const int T = ts / ksteps, S = ts - T * ksteps, row = 32 * T + (lane & 31);
-        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (row < rows) {
-            const float *wr = W + (size_t)row * cols;
-            if (l == 0) {
-                // eight consecutive floats of an in_dim-float row (19 or 20; the critic's: 25 or 26)
-                #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int k = actor_k_of(0, S, h, j);
-                    if (k < cols) v[j] = wr[k];
-                }
-            } else {
-                // two runs of four (cols is a multiple of 32, so both lie inside the row)
-                const actor_f32x4u a0 = *reinterpret_cast<const actor_f32x4u *>(wr + actor_k_of(l, S, h, 0));
-                const actor_f32x4u a1 = *reinterpret_cast<const actor_f32x4u *>(wr + actor_k_of(l, S, h, 4));
-                #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    v[j] = a0[j];
-                    v[4 + j] = a1[j];
-                }
-            }
-        }
-        uint32_t w[4];
-        #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            w[j] = (uint32_t)actor_bf16_bits(v[2 * j]) | ((uint32_t)actor_bf16_bits(v[2 * j + 1]) << 16);    // +0 -> 0
-        out = {w[0], w[1], w[2], w[3]};
-    }
-    static_cast<uint4 *>(blob)[i] = out;
+    for (int m = 0; m < ACTOR_LAYERS; ++m)
+        if (m == it.l) p = it.bias ? src.b[m] : src.W[m];
+    float v[8];
+    actor_item_load(it, p, v);
+    static_cast<uint4 *>(blob)[i] = actor_item_pack(it, v);
 }
 
 // The launch of ctr_actor_load / ctr_critic_load (`fn`), after the shape checks: ak.blob not yet set.

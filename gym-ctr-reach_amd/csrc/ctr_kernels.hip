@@ -22,6 +22,8 @@
 //                 layer (ctr_critic; ctr_critic.inc)
 //   k_her_sample_td  k_her_sample, then the target policy, the target critic and the DDPG target of
 //                 every sampled row, the two blobs taking turns in LDS (ctr_her_sample_td; ctr_critic.inc)
+//   k_polyak      the soft update of up to four target networks' f32 parameters in place and their
+//                 blobs repacked from the result, k_actor_load's mapping (ctr_polyak; ctr_polyak.inc)
 //   k_collect     k_rollout with exploration noise on each action and each step recorded into the HER
 //                 store (ctr_collect, at the end of the file)
 //   k_explore     the exploration noise alone, one env per lane (ctr_explore; explore_lane, ctr_device.hpp)
@@ -3195,3 +3197,4 @@ int ctr_follow(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_
 }  // extern "C"
 
 #include "ctr_critic.inc"
+#include "ctr_polyak.inc"

@@ -17,6 +17,6 @@ from .systems import Tube, default_kwargs, default_systems_parameters  # noqa: F
 from .goal_tolerance import GoalTolerance  # noqa: F401
 from .ik import dls_ik_path, dls_ik_position_only  # noqa: F401
 from .her import HerReplayBuffer  # noqa: F401
-from .policy import MlpActor, MlpCritic  # noqa: F401
+from .policy import MlpActor, MlpCritic, polyak_  # noqa: F401
 from .paths import circle_path, helix_path, line_path  # noqa: F401
 from . import paths  # noqa: F401

@@ -11,10 +11,14 @@ reference's stable-baselines DDPG ``MlpPolicy`` actor on HERGoalEnvWrapper's fla
 
 ``MlpCritic`` is the Q-network on the same kernels (ctr_critic; ``HerReplayBuffer.sample_td`` runs a
 target policy and a target critic on every sampled row and returns the DDPG target with the batch).
+``polyak_`` is the soft update of such target networks' float32 parameters together with the
+refresh of their blobs, one launch for all of them (ctr_polyak).
 
 ``ExploreNoise`` is the exploration noise of the reference's DDPG + HER training on such an actor's
 actions (ctr_explore / ctr_collect), with its own numpy restatement.
 """
+import ctypes
+
 import numpy as np
 
 from . import _abi, _abi_critic
@@ -75,6 +79,51 @@ class _Mlp(object):
     def _fn(self, what):
         return "ctr_%s_%s" % (self.NAME, what)
 
+    def _device_layers(self, layers, role="", target=False):
+        """The checks of ``load_`` and ``polyak_`` on one list of device parameters: ``layers`` as
+        ``load_`` takes them -> [(W, b), ...] detached.  Every tensor on the network's device,
+        float32, of its shape and contiguous, or ValueError (``role`` names the list in the
+        messages); nothing is converted.  ``target``: the tensors will be written, so none may
+        require grad."""
+        import torch
+        if self.blob is None:
+            raise RuntimeError("%s is on the host (%s(..., device=None)): nothing to load into"
+                               % (self._A, type(self).__name__))
+        if isinstance(layers, torch.nn.Module):
+            layers = _sequential_layers(layers, self.TANH, self.NAME, detach=False)
+        layers = [tuple(pair) for pair in layers]
+        dims = [self.in_dim] + self.hidden + [self.OUT]
+        if len(layers) != len(dims) - 1 or any(len(pair) != 2 for pair in layers):
+            raise ValueError("%s%s has %d layers of (W, b)" % (role, self._A, len(dims) - 1))
+        src = []
+        for l, (W, b) in enumerate(layers):
+            pair = []
+            for name, t, shape in (("W", W, (dims[l + 1], dims[l])), ("b", b, (dims[l + 1],))):
+                what = "%slayer %d: %s" % (role, l, name)
+                if not isinstance(t, torch.Tensor):
+                    raise ValueError(what + " must be a torch tensor")
+                if t.device.type != self.device.type or (self.device.index is not None
+                                                         and t.device.index != self.device.index):
+                    raise ValueError("%s is on %s, %s on %s" % (what, t.device, self._A, self.device))
+                if t.dtype != torch.float32:
+                    raise ValueError("%s must be float32, not %s" % (what, t.dtype))
+                if tuple(t.shape) != shape:
+                    raise ValueError("%s must be %s, not %s" % (what, list(shape), list(t.shape)))
+                if not t.is_contiguous():
+                    raise ValueError(what + " must be contiguous")
+                if target and t.requires_grad:
+                    raise ValueError(what + " requires grad: a target is written in place, outside autograd")
+                pair.append(t.detach())
+            src.append(tuple(pair))
+        return src
+
+    def polyak_(self, online, target, tau, stream=None):
+        """The one-net case of the module's ``polyak_``: ``target`` moves towards ``online`` by
+        ``tau`` in place and this network's blob becomes the pack of the new ``target``, in one
+        launch.  Returns self."""
+        polyak_([(self, online, target)], tau, stream)
+        return self
+
     def load_(self, layers, stream=None, keep_host=False):
         """Refresh the device blob in place from device-resident parameters (ctr_actor_load /
         ctr_critic_load): one launch on ``stream`` (default: the current stream), ordered like any
@@ -89,34 +138,7 @@ class _Mlp(object):
         ``emulate`` / ``reference`` raise until a load with ``keep_host=True``, which copies the
         sources back to the host and therefore SYNCHRONISES (not for a captured graph).  Returns
         self."""
-        import torch
-        if self.blob is None:
-            raise RuntimeError("%s is on the host (%s(..., device=None)): nothing to load into"
-                               % (self._A, type(self).__name__))
-        if isinstance(layers, torch.nn.Module):
-            layers = _sequential_layers(layers, self.TANH, self.NAME)
-        layers = [tuple(pair) for pair in layers]
-        dims = [self.in_dim] + self.hidden + [self.OUT]
-        if len(layers) != len(dims) - 1 or any(len(pair) != 2 for pair in layers):
-            raise ValueError("%s has %d layers of (W, b)" % (self._A, len(dims) - 1))
-        src = []
-        for l, (W, b) in enumerate(layers):
-            pair = []
-            for name, t, shape in (("W", W, (dims[l + 1], dims[l])), ("b", b, (dims[l + 1],))):
-                what = "layer %d: %s" % (l, name)
-                if not isinstance(t, torch.Tensor):
-                    raise ValueError(what + " must be a torch tensor")
-                if t.device.type != self.device.type or (self.device.index is not None
-                                                         and t.device.index != self.device.index):
-                    raise ValueError("%s is on %s, %s on %s" % (what, t.device, self._A, self.device))
-                if t.dtype != torch.float32:
-                    raise ValueError("%s must be float32, not %s" % (what, t.dtype))
-                if tuple(t.shape) != shape:
-                    raise ValueError("%s must be %s, not %s" % (what, list(shape), list(t.shape)))
-                if not t.is_contiguous():
-                    raise ValueError(what + " must be contiguous")
-                pair.append(t.detach())
-            src.append(tuple(pair))
+        src = self._device_layers(layers)
         n = len(src)
         W = (_abi._P * n)(*[w.data_ptr() for w, _ in src])
         b = (_abi._P * n)(*[v.data_ptr() for _, v in src])
@@ -410,9 +432,64 @@ class ExploreNoise(object):
         return np.where(rnd[:, None], uniform.astype(np.float64), gauss)
 
 
-def _sequential_layers(seq, tanh=True, name="actor"):
-    """[(W, b), ...] (detached) of an ``nn.Sequential`` of Linear, ReLU, ..., Linear, then Tanh (the
-    actor) or nothing (the critic)."""
+def polyak_(nets, tau, stream=None):
+    """The soft (Polyak) update of 1..4 target networks and the refresh of their device blobs in one
+    launch (ctr_polyak).  ``nets``: a list of triples ``(net, online, target)``: ``net`` the device
+    ``MlpActor`` / ``MlpCritic`` that holds the TARGET network's blob, ``online`` and ``target`` the
+    learner's and the target's float32 parameters as ``load_`` takes them ([(W, b), ...] or an
+    ``nn.Sequential``).  For every element, torch's ``lerp`` in float32 without fused multiply-add
+    (include/ctr_reach_amd.h):
+
+        target <- target + tau * (online - target)              (tau < 0.5)
+        target <- online - (online - target) * (1 - tau)        (otherwise)
+
+    stored over ``target``, and each net's blob becomes what ``net.load_(target)`` would make of the
+    result.  It replaces the trainer's ``lerp_`` loop and the ``load_`` of each target:
+
+        polyak_([(actor_targ, policy, policy_targ), (critic_targ_dev, critic, critic_targ)], 0.001)
+
+    One launch on ``stream`` (default: the current stream); no allocation, no copy to the host and
+    no synchronisation, so it can be captured into a graph.  Every tensor is checked as ``load_``
+    checks it (ValueError, nothing converted, nothing written); a target tensor must not require
+    grad, since it is written behind autograd's back; a host-only net raises RuntimeError.
+    Afterwards each net's sources are its target tensors and its host copies (``weights``,
+    ``biases``, ``packed``) are dropped, as ``load_`` drops them; ``net.load_(target,
+    keep_host=True)`` brings them back."""
+    from . import _abi_polyak
+    nets = [tuple(n) for n in nets]
+    if not 1 <= len(nets) <= _abi_polyak.CTR_POLYAK_MAX_NETS or any(len(n) != 3 for n in nets):
+        raise ValueError("nets is a list of 1..%d triples (net, online, target)" % _abi_polyak.CTR_POLYAK_MAX_NETS)
+    tau = float(tau)
+    if not 0.0 <= tau <= 1.0:
+        raise ValueError("tau must be in [0, 1]")
+    arr = (_abi_polyak.CtrPolyakNet * len(nets))()
+    device, done = None, []
+    for m, (net, online, target) in enumerate(nets):
+        if not isinstance(net, _Mlp):
+            raise ValueError("net %d must be an MlpActor or an MlpCritic" % m)
+        on = net._device_layers(online, "net %d: online " % m)
+        tg = net._device_layers(target, "net %d: target " % m, target=True)
+        if device is not None and net.device != device:
+            raise ValueError("net %d is on %s, net 0 on %s" % (m, net.device, device))
+        device = net.device
+        n = len(on)
+        a = arr[m]
+        setattr(a, net.NAME, ctypes.pointer(net._struct))
+        a.W = (_abi._P * n)(*[w.data_ptr() for w, _ in on])
+        a.b = (_abi._P * n)(*[v.data_ptr() for _, v in on])
+        a.W_targ = (_abi._P * n)(*[w.data_ptr() for w, _ in tg])
+        a.b_targ = (_abi._P * n)(*[v.data_ptr() for _, v in tg])
+        done.append((net, tg))
+    rc = _abi.load().ctr_polyak(arr, len(nets), tau, _abi.stream_ptr(stream, device.index))
+    _abi.check(rc, "ctr_polyak")
+    for net, tg in done:
+        net._sources = tg
+        net.weights = net.biases = net.packed = None
+
+
+def _sequential_layers(seq, tanh=True, name="actor", detach=True):
+    """[(W, b), ...] (detached, or with ``detach`` False the parameters themselves) of an
+    ``nn.Sequential`` of Linear, ReLU, ..., Linear, then Tanh (the actor) or nothing (the critic)."""
     import torch.nn as nn
     mods = list(seq)
     if tanh:
@@ -426,7 +503,7 @@ def _sequential_layers(seq, tanh=True, name="actor"):
         if i % 2 == 0:
             if not isinstance(m, nn.Linear) or m.bias is None:
                 raise ValueError("module %d must be an nn.Linear with a bias" % i)
-            layers.append((m.weight.detach(), m.bias.detach()))
+            layers.append((m.weight.detach(), m.bias.detach()) if detach else (m.weight, m.bias))
         elif not isinstance(m, nn.ReLU):
             raise ValueError("module %d must be an nn.ReLU" % i)
     if len(mods) % 2 == 0:

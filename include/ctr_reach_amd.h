@@ -40,6 +40,9 @@
  *                       _train_step: r + gamma (1 - done) Q'(s', pi'(s')) from the target networks,
  *                       ctr_her_sample_td together with the replay draw that feeds it
  *                       (ctr_critic_load: the Polyak-updated target parameters into the critic's blob)
+ *   ctr_polyak          the target update of that DDPG (ddpg.py get_target_updates: target <-
+ *                       (1 - tau) target + tau online after every training step) together with the
+ *                       refresh of the target networks' blobs, one launch for all of them
  *   ctr_explore / ctr_collect
  *                       the data collection of the reference's training pipeline, stable-baselines
  *                       DDPG under HER: NormalActionNoise clipped to the action box and
@@ -735,6 +738,40 @@ typedef struct ctr_her_td_t {
 } ctr_her_td_t;
 int ctr_her_sample_td(const ctr_her_t *her, int64_t batch_size, uint64_t seed, uint64_t counter,
                       const ctr_her_batch_t *out, const ctr_her_td_t *td, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The soft (Polyak) update of target networks and the refresh of their blobs, in one launch for up
+ * to CTR_POLYAK_MAX_NETS networks (added within ABI 17: a new symbol, no entry point or struct
+ * changes).  For every element of every target tensor, with p the online value and t the target's,
+ *     tau <  0.5:  t' = t + tau * (p - t)
+ *     otherwise:   t' = p - (p - t) * (1 - tau)
+ * (torch.lerp's formula), every operation rounded to f32 and no fused multiply-add, so a float32
+ * restatement in numpy gives the same bits.  t' is stored over t, and the net's blob is overwritten
+ * with the bytes ctr_actor_pack / ctr_critic_pack would give for the new target parameters, padding
+ * included: ctr_actor_load / ctr_critic_load of the updated targets, without their launches.  At
+ * tau == 1 the formula gives t' = p exactly wherever p - t is finite and p is not -0 (the product
+ * is then a zero, and only -0 changes when a zero is subtracted from it); at tau == 0 it likewise
+ * gives t wherever p - t is finite and t is not -0.
+ * The mapping is ctr_actor_load's: one thread per 16 B of a blob owns the eight weights or four
+ * bias floats that item packs.  The fragment layout covers each (row, k) of a layer once, so each
+ * target element is read and written by exactly one thread and the update in place needs no
+ * ordering inside the launch; the online tensors are only read.  One launch on `stream`, nothing
+ * read back, no allocation: it can be captured into a graph.
+ * Refused (CTR_EINVAL, before any HIP call, ctr_last_error names ctr_polyak): nets NULL; n_nets
+ * outside 1..CTR_POLYAK_MAX_NETS; a net with both or neither of actor / critic; a shape, scale or
+ * blob that ctr_actor / ctr_critic would refuse; a NULL pointer array or a NULL layer in
+ * 0..n_hidden; W[l] == W_targ[l] or b[l] == b_targ[l] (online and target are the same tensor); two
+ * nets with the same blob; tau NaN or outside [0, 1]. */
+#define CTR_POLYAK_MAX_NETS 4
+typedef struct ctr_polyak_net_t {
+    const ctr_actor_t  *actor;      /* exactly one of actor / critic is non-NULL: the   */
+    const ctr_critic_t *critic;     /* TARGET network's shape and its device blob        */
+    const float *const *W;          /* online parameters, device, [n_hidden + 1] layers  */
+    const float *const *b;
+    float *const *W_targ;           /* target parameters (the f32 masters), device,      */
+    float *const *b_targ;           /* updated in place                                   */
+} ctr_polyak_net_t;
+int ctr_polyak(const ctr_polyak_net_t *nets, int32_t n_nets, float tau, void *stream);
 
 /* CtrReachEnv.reset for the environments with mask[i] != 0 (mask NULL = all).
  * goal [n][3] or NULL (sample a goal), system [n] or NULL (sample uniformly).
