@@ -282,9 +282,12 @@ __device__ __forceinline__ Trig trig_of(const double al[3])
             t.c20 = r.c;
         }
     }
-    // alpha_2 - alpha_1 = (alpha_2 - alpha_0) - (alpha_1 - alpha_0): angle-difference identity
-    t.c21 = t.c20 * t.c10 + t.s20 * t.s10;
-    t.s21 = t.s20 * t.c10 - t.c20 * t.s10;
+    // alpha_2 - alpha_1 = (alpha_2 - alpha_0) - (alpha_1 - alpha_0): angle-difference identity.
+    // The fma is explicit: left to contraction, the compiler fused c20 c10 in the CAREFUL = false
+    // instantiation and s20 s10 in the CAREFUL = true one, so c21 differed in its last bit between
+    // the two (tests/test_gpu_math.py::test_trig_of).  These are the CAREFUL = false forms.
+    t.c21 = fma(t.c20, t.c10, t.s20 * t.s10);
+    t.s21 = fma(t.s20, t.c10, -(t.c20 * t.s10));
     return t;
 }
 

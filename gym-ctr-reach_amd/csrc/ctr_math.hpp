@@ -3,7 +3,13 @@
 // sincos_cw: Cody-Waite reduction by pi/2 (three FMA terms) + fdlibm-style minimax kernels on
 // [-pi/4, pi/4]; sine and cosine share one reduction.  Arguments beyond |x| < 2^20 (never
 // reached by joint angles, which are bounded by the action limits and episode length) fall
-// back to the math library.  Max error <= 2 ulp is checked on the host by tests/test_math.py.
+// back to the math library.  Asserted: <= 2 ulp where |value| > 1e-3 and < 4e-16 absolute.
+//
+// Who checks what: tests/test_math.py compiles this header for the host without FMA contraction,
+// i.e. the #else of every #if defined(__HIP_DEVICE_COMPILE__) below; tests/test_gpu_math.py runs the
+// device branches, contracted as the product's flags contract them, on the GPU.  sincos_cw is the
+// one sincos whose bits differ between the two builds (its polynomial sums contract); measured on
+// the device: 1.4 ulp, 1.2e-16 absolute (mpmath reference).
 #pragma once
 #include <math.h>
 
@@ -72,7 +78,10 @@ CTR_HD bool sincos_needs_slow(double x) { return !(fabs(x) < 1048576.0); }
 // two-term Cody-Waite reduction (the third pi/256 term is below 1e-28 for |x| < 2^20): 14 fp64
 // operations per angle, no quadrant selects.  One wave per SIMD makes the FK loop issue-bound,
 // so every operation counts (the pi/64 table with degree-7 / 6 kernels took 16).  Max error
-// <= 2 ulp (tests/test_math.py).  Valid for |x| < 2^20 like sincos_fast.
+// <= 2 ulp (tests/test_math.py).  Valid for |x| < 2^20 like sincos_fast.  Every operation below is
+// an explicit fma, a lone product or rint, so contraction changes nothing: the device results are
+// the host build's bit for bit (tests/test_gpu_math.py; measured 1.83 ulp, 2.1e-16 absolute).
+// The table entries are correctly rounded, with exact 0 and +-1 at k = 0, 128, 256, 384.
 #include "ctr_trig_tab512.inc"
 
 // Split in two so callers can issue the reduction and the table loads a stage ahead of the
@@ -137,22 +146,10 @@ CTR_HD void sincos_cw(double x, double *sp, double *cp)
     sincos_fast(x, *sp, *cp);
 }
 
-// 1/x to within 1 ulp: hardware reciprocal estimate + two Newton-Raphson steps.
-CTR_HD double rcp(double x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    double r = __builtin_amdgcn_rcp(x);
-    double e = fma(-x, r, 1.0);
-    r = fma(r, e, r);
-    e = fma(-x, r, 1.0);
-    return fma(r, e, r);
-#else
-    return 1.0 / x;
-#endif
-}
-
 // max(|a|, |b|) as one v_max_f64 with abs modifiers (fmax() would first canonicalize each
 // loop-carried operand with an extra v_max: the error scales of the step controller).
+// Equal to fmax(fabs(a), fabs(b)) bit for bit, subnormals included; with one quiet NaN operand the
+// hardware returns the other operand's magnitude (as fmax does), with a signalling NaN a NaN.
 CTR_HD double absmax(double a, double b)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -164,7 +161,10 @@ CTR_HD double absmax(double a, double b)
 #endif
 }
 
-// 1/x to about 1 ulp with a single Newton-Raphson step (step-size control only).
+// 1/x with a single Newton-Raphson step on the estimate (the initial step size only): relative
+// error <= 2^-48 + 2^-52 = 3.8e-15, the square of rcp_est's 2^-24 plus the step's roundings;
+// measured on the device 2.1e-15 (2^-48.8), 10.6 ulp.  Not "about 1 ulp": that needs a second step.
+// rcp1(0) is inf or NaN; select_initial_step discards it (d1sq < 1e-10 selects h0 = 1e-6).
 CTR_HD double rcp1(double x)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -175,7 +175,8 @@ CTR_HD double rcp1(double x)
 #endif
 }
 
-// 1/x as the bare v_rcp_f64 estimate (relative error <= 2^-24, tools/ubench/rcp_acc: max 2.6e8 ulp).
+// 1/x as the bare v_rcp_f64 estimate (relative error <= 2^-24, asserted by tests/test_gpu_math.py,
+// which measured 4.5e-8 = 2^-24.4, 2.5e8 ulp; tools/ubench/rcp_acc: max 2.6e8 ulp).
 // Used only for the 18 error scales 1/(atol + |y| rtol) of the RK45 step controller: the error
 // norm, and from it the accept/reject decision and the next step size, then carry a relative
 // error below 6e-8, which moves h by < 1.2e-8 relative (the tip by ~1e-12 m) and flips an
@@ -189,8 +190,9 @@ CTR_HD double rcp_est(double x)
 #endif
 }
 
-// x^(-1/10) for finite x > 0, ~1 ulp: x = x' 2^(10k) with x' in [1, 2^10); a float32
-// exp2/log2 seed for x'^(-1/10), two float64 Newton steps on y^10 x' = 1, then 2^(-k).
+// x^(-1/10) for finite x > 0 (asserted <= 2 ulp, subnormals included; measured 0.98 ulp with the
+// device's v_log_f32 / v_exp_f32 seed, 0.96 with the host's): x = x' 2^(10k) with x' in [1, 2^10); a
+// float32 exp2/log2 seed for x'^(-1/10), two float64 Newton steps on y^10 x' = 1, then 2^(-k).
 // (Replaces pow(), ~5x cheaper; used by the RK45 step-size controller only.)
 CTR_HD double inv_root10(double x)
 {
@@ -231,7 +233,8 @@ CTR_HD double gap_up(double t)
     return (t == -INFINITY || t == 1.7976931348623157e308) ? INFINITY : g + 0.0 * t;
 }
 
-// sqrt(x) for finite x > 0, ~1 ulp: reciprocal square root estimate + Newton (no division).
+// sqrt(x) for finite x > 0: reciprocal square root estimate + Newton (no division).  Asserted
+// <= 2 ulp on 10^U(-30, 30); measured on the device (v_rsq_f64 seed): all 100 000 correctly rounded.
 CTR_HD double sqrt_rsq(double x)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
