@@ -36,9 +36,17 @@ become one ``polyak_`` call, one launch that updates the float32 target paramete
 repacks both blobs from them.  The torch target modules still own those parameters, so their
 ``state_dict()`` is what it was.
 
+With ``--device-update`` (``main(..., device_update=True)``, which implies ``--device-polyak``) step 3
+leaves torch as well: the online networks are built with ``requires_grad_(False)`` and no torch
+optimiser, and a ``DdpgLearner`` (ctr_reach_amd/learner.py) makes the critic's step (forward, MSE
+against ``target``, backward, Adam) and the policy's step (policy forward, critic forward, backward
+through both, Adam), two launches each, in float32 on those parameters in place.  An update is then
+``sample_td``, ``critic_step``, ``actor_step`` and ``polyak_``, none of it autograd; the action is
+divided by ``scale`` inside ``critic_step``.  The modules still own the parameters.
+
 usage: python examples/train_ddpg_her.py [--num-envs N] [--iterations I] [--steps-per-iter S]
            [--batch-size B] [--updates-per-iter U] [--hidden 64,64] [--seed 0] [--device cuda]
-           [--device-targets] [--device-polyak]"""
+           [--device-targets] [--device-polyak] [--device-update]"""
 import argparse
 import os
 import sys
@@ -50,6 +58,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-ctr-reach_amd"))
 from ctr_reach_amd import CtrReachVecEnv  # noqa: E402
+from ctr_reach_amd.learner import DdpgLearner  # noqa: E402
 from ctr_reach_amd.policy import ExploreNoise, MlpActor, MlpCritic, polyak_  # noqa: E402
 
 GAMMA, TAU, ACTOR_LR, CRITIC_LR = 0.99, 0.001, 1e-4, 1e-3
@@ -69,8 +78,9 @@ def mlp(n_in, hidden, n_out, tanh):
 
 
 def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, updates_per_iter=40, hidden=(64, 64), seed=0,
-         device="cuda", device_targets=False, device_polyak=False):
+         device="cuda", device_targets=False, device_polyak=False, device_update=False):
     device = torch.device(device)
+    device_polyak = device_polyak or device_update
     device_targets = device_targets or device_polyak
     torch.manual_seed(seed)
     venv = CtrReachVecEnv(num_envs, device=device, seed=seed)
@@ -88,8 +98,15 @@ def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, update
     critic_targ.load_state_dict(critic.state_dict())
     for p in list(policy_targ.parameters()) + list(critic_targ.parameters()):
         p.requires_grad_(False)
-    policy_opt = torch.optim.Adam(policy.parameters(), lr=ACTOR_LR)
-    critic_opt = torch.optim.Adam(critic.parameters(), lr=CRITIC_LR)
+    learner = None
+    if device_update:                                                        # the masters are written by the kernels
+        policy.requires_grad_(False)
+        critic.requires_grad_(False)
+        learner = DdpgLearner(policy, critic, scale=venv.action_space.high, actor_lr=ACTOR_LR, critic_lr=CRITIC_LR,
+                              max_batch=batch_size)
+    else:
+        policy_opt = torch.optim.Adam(policy.parameters(), lr=ACTOR_LR)
+        critic_opt = torch.optim.Adam(critic.parameters(), lr=CRITIC_LR)
 
     actor = MlpActor.from_torch(policy, venv.action_space.high, device)      # once; load_ from here on
     noise = ExploreNoise(SIGMA, random_eps=RANDOM_EPS, seed=seed)
@@ -103,6 +120,14 @@ def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, update
         critic_sum = torch.zeros((), device=device)
         policy_sum = torch.zeros((), device=device)
         for _ in range(updates_per_iter):
+            if device_update:                                                # sample_td, two steps, polyak_: no autograd
+                batch = her.sample_td(batch_size, actor_targ, critic_targ_dev, GAMMA)
+                learner.critic_step(batch["obs"], batch["action"], batch["target"])
+                learner.actor_step(batch["obs"])
+                polyak_([(actor_targ, policy, policy_targ), (critic_targ_dev, critic, critic_targ)], TAU)
+                critic_sum += learner.critic_loss
+                policy_sum += learner.actor_loss
+                continue
             if device_targets:
                 batch = her.sample_td(batch_size, actor_targ, critic_targ_dev, GAMMA)
                 obs, target = batch["obs"], batch["target"]
@@ -136,7 +161,7 @@ def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, update
         # the iteration's only host read
         losses.append((critic_sum.item() / max(updates_per_iter, 1), policy_sum.item() / max(updates_per_iter, 1)))
     return dict(actor=actor, policy=policy, critic=critic, policy_targ=policy_targ, critic_targ=critic_targ,
-                actor_targ=actor_targ, critic_targ_dev=critic_targ_dev, losses=losses,
+                actor_targ=actor_targ, critic_targ_dev=critic_targ_dev, learner=learner, losses=losses,
                 rollout_stats=venv.rollout_stats, venv=venv, her=her)
 
 
@@ -153,10 +178,12 @@ if __name__ == "__main__":
     ap.add_argument("--device-targets", action="store_true", help="the DDPG target from her.sample_td (bf16 target networks)")
     ap.add_argument("--device-polyak", action="store_true",
                     help="the Polyak update and both blob refreshes in one polyak_ launch (implies --device-targets)")
+    ap.add_argument("--device-update", action="store_true",
+                    help="the critic's and the policy's updates from a DdpgLearner, no autograd (implies --device-polyak)")
     args = ap.parse_args()
     out = main(args.num_envs, args.iterations, args.steps_per_iter, args.batch_size, args.updates_per_iter,
                tuple(int(w) for w in args.hidden.split(",")), args.seed, args.device, args.device_targets,
-               args.device_polyak)
+               args.device_polyak, args.device_update)
     for it, (c, p) in enumerate(out["losses"]):
         print("iteration %3d: critic loss %.4g, policy loss %.4g" % (it, c, p))
     stats = out["rollout_stats"]

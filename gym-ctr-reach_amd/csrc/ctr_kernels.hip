@@ -24,6 +24,10 @@
 //                 every sampled row, the two blobs taking turns in LDS (ctr_her_sample_td; ctr_critic.inc)
 //   k_polyak      the soft update of up to four target networks' f32 parameters in place and their
 //                 blobs repacked from the result, k_actor_load's mapping (ctr_polyak; ctr_polyak.inc)
+//   k_ddpg_grad   DDPG's critic or policy loss on tiles of 16 rows, forward and backward in f32 on the
+//                 f32 matrix instructions, the weight gradients summed per workgroup into workspace slots;
+//   k_ddpg_apply  the slots summed per parameter, the gradient stored and one Adam step made
+//                 (ctr_ddpg_critic_step, ctr_ddpg_actor_step; ctr_ddpg.inc)
 //   k_collect     k_rollout with exploration noise on each action and each step recorded into the HER
 //                 store (ctr_collect, at the end of the file)
 //   k_explore     the exploration noise alone, one env per lane (ctr_explore; explore_lane, ctr_device.hpp)
@@ -3198,3 +3202,4 @@ int ctr_follow(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_
 
 #include "ctr_critic.inc"
 #include "ctr_polyak.inc"
+#include "ctr_ddpg.inc"

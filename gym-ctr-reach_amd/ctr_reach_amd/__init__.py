@@ -9,6 +9,7 @@ with the environments stepped in lockstep by hand-written HIP kernels on gfx950.
   make             make('CTR-Reach-v0', **overrides)
   HerReplayBuffer  device HER replay feed (stable-baselines 2 'future' relabelling)
   MlpActor         the policy's actor, run by hand-written kernels (rollout, collect, follow)
+  DdpgLearner      DDPG's critic and actor updates (forward, backward, Adam) on the device
   paths            line / circle / helix waypoint paths for follow() and dls_ik_path
 """
 from .vec_env import CtrReachVecEnv, FollowResult  # noqa: F401
@@ -18,5 +19,6 @@ from .goal_tolerance import GoalTolerance  # noqa: F401
 from .ik import dls_ik_path, dls_ik_position_only  # noqa: F401
 from .her import HerReplayBuffer  # noqa: F401
 from .policy import MlpActor, MlpCritic, polyak_  # noqa: F401
+from .learner import DdpgLearner  # noqa: F401
 from .paths import circle_path, helix_path, line_path  # noqa: F401
 from . import paths  # noqa: F401

@@ -1,0 +1,264 @@
+"""DDPG's two updates on the device (ctr_ddpg_critic_step / ctr_ddpg_actor_step,
+include/ctr_reach_amd.h): forward, loss, backward and Adam of the critic's regression on the target
+and of the policy's ascent on Q(s, pi(s)), two launches each, in float32 on the learner's own
+parameters.  No autograd and no torch optimiser:
+
+    learner = DdpgLearner(policy, critic, scale=venv.action_space.high)
+    batch = buf.sample_td(256, actor_targ, critic_targ, gamma)
+    learner.critic_step(batch["obs"], batch["action"], batch["target"])
+    learner.actor_step(batch["obs"])
+    polyak_([(actor_targ, policy, policy_targ), (critic_targ_dev, critic, critic_targ)], 0.001)
+
+``adam_reference`` is the numpy float32 restatement of the Adam step (the kernel gives its bits).
+"""
+import ctypes
+
+import numpy as np
+
+from . import _abi, _abi_critic
+
+
+def adam_reference(p, g, m, v, pow, lr, betas=(0.9, 0.999), eps=1e-8):
+    """One Adam step as the header states it, every operation a float32 numpy operation (one rounding
+    each): (p', m', v', pow') from float32 arrays p, g, m, v and pow = [beta1^t, beta2^t]."""
+    f = np.float32
+    p, g, m, v = (np.asarray(a, dtype=f) for a in (p, g, m, v))
+    b1, b2, lr, eps, one = f(betas[0]), f(betas[1]), f(lr), f(eps), f(1)
+    pw = np.asarray(pow, dtype=f)
+    pw1, pw2 = pw[0] * b1, pw[1] * b2
+    m1 = (b1 * m) + ((one - b1) * g)
+    v1 = (b2 * v) + (((one - b2) * g) * g)
+    with np.errstate(all="ignore"):
+        p1 = p - lr * ((m1 / (one - pw1)) / (np.sqrt(v1 / (one - pw2)) + eps))
+    assert p1.dtype == m1.dtype == v1.dtype == f
+    return p1, m1, v1, np.array([pw1, pw2], dtype=f)
+
+
+def _layers_of(net, tanh, name):
+    """[(W, b), ...] of an ``nn.Sequential`` (the parameters themselves) or of such a list."""
+    import torch
+    from .policy import _sequential_layers
+    if isinstance(net, torch.nn.Module):
+        return _sequential_layers(net, tanh, name, detach=False)
+    layers = [tuple(pair) for pair in net]
+    if any(len(pair) != 2 for pair in layers):
+        raise ValueError("the %s is an nn.Sequential or a list of (W, b)" % name)
+    return layers
+
+
+def _masters(net, tanh, name, in_dims, out, in_msg):
+    """The checks of ``_Mlp._device_layers`` on a learning network: every tensor a float32, contiguous
+    torch tensor of its shape on one device that does not require grad (it is written in place, outside
+    autograd); nothing is converted.  -> ([(W, b), ...] detached, in_dim, hidden)."""
+    import torch
+    layers = _layers_of(net, tanh, name)
+    if not 2 <= len(layers) <= _abi.CTR_ACTOR_MAX_HIDDEN + 1:
+        raise ValueError("the %s has 1..%d hidden layers and an output layer" % (name, _abi.CTR_ACTOR_MAX_HIDDEN))
+    for l, (W, b) in enumerate(layers):
+        for what, t in (("W", W), ("b", b)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("%s layer %d: %s must be a torch tensor" % (name, l, what))
+    W0 = layers[0][0]
+    if W0.dim() != 2 or W0.shape[1] not in in_dims:
+        raise ValueError(in_msg)
+    in_dim = int(W0.shape[1])
+    hidden = [int(W.shape[0]) for W, _ in layers[:-1]]
+    for w in hidden:
+        if w % 32 or not 32 <= w <= _abi.CTR_ACTOR_MAX_WIDTH:
+            raise ValueError("%s: hidden widths must be multiples of 32 in 32..%d" % (name, _abi.CTR_ACTOR_MAX_WIDTH))
+    dims = [in_dim] + hidden + [out]
+    src, device = [], None
+    for l, (W, b) in enumerate(layers):
+        pair = []
+        for what, t, shape in (("W", W, (dims[l + 1], dims[l])), ("b", b, (dims[l + 1],))):
+            what = "%s layer %d: %s" % (name, l, what)
+            if t.dtype != torch.float32:
+                raise ValueError("%s must be float32, not %s" % (what, t.dtype))
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must be %s, not %s" % (what, list(shape), list(t.shape)))
+            if not t.is_contiguous():
+                raise ValueError(what + " must be contiguous")
+            if t.requires_grad:
+                raise ValueError(what + " requires grad: the learner writes it in place, outside autograd")
+            if device is not None and t.device != device:
+                raise ValueError("%s is on %s, the rest of the %s on %s" % (what, t.device, name, device))
+            device = t.device
+            pair.append(t.detach())
+        src.append(tuple(pair))
+    return src, in_dim, hidden
+
+
+class _Net(object):
+    """One learning network: its masters, gradients, Adam state and their ctr_ddpg_net_t."""
+
+    def __init__(self, params, alloc, lr, betas, eps):
+        import torch
+        from . import _abi_ddpg
+        self.params = params
+        self.grads = [(alloc(tuple(W.shape)), alloc(tuple(b.shape))) for W, b in params]
+        self.m = [(alloc(tuple(W.shape)), alloc(tuple(b.shape))) for W, b in params]
+        self.v = [(alloc(tuple(W.shape)), alloc(tuple(b.shape))) for W, b in params]
+        self.pow = torch.ones(2, dtype=torch.float32, device=params[0][0].device)
+        n = len(params)
+        self.arrays = {}
+        self.struct = s = _abi_ddpg.CtrDdpgNet()
+        for field, src, which in (("W", params, 0), ("b", params, 1), ("gW", self.grads, 0), ("gb", self.grads, 1),
+                                  ("mW", self.m, 0), ("mb", self.m, 1), ("vW", self.v, 0), ("vb", self.v, 1)):
+            for pair in src:
+                t = pair[which]
+                if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous()
+                        and t.device == params[0][0].device):
+                    raise ValueError("alloc must return contiguous float32 tensors on the networks' device")
+            self.arrays[field] = arr = (_abi._P * n)(*[pair[which].data_ptr() for pair in src])
+            setattr(s, field, arr)
+        s.pow = self.pow.data_ptr()
+        self.adam = _abi_ddpg.CtrDdpgAdam(float(lr), float(betas[0]), float(betas[1]), float(eps))
+
+    def state(self):
+        return {"m": [(a.clone(), b.clone()) for a, b in self.m], "v": [(a.clone(), b.clone()) for a, b in self.v],
+                "pow": self.pow.clone()}
+
+    def load_state(self, state):
+        for name, mine in (("m", self.m), ("v", self.v)):
+            theirs = state[name]
+            if len(theirs) != len(mine):
+                raise ValueError("state: %s has %d layers, the network %d" % (name, len(theirs), len(mine)))
+            for (a, b), (a1, b1) in zip(mine, theirs):
+                if tuple(a1.shape) != tuple(a.shape) or tuple(b1.shape) != tuple(b.shape):
+                    raise ValueError("state: a tensor of %s has another shape" % name)
+        if tuple(state["pow"].shape) != (2,):
+            raise ValueError("state: pow must have 2 elements")
+        for name, mine in (("m", self.m), ("v", self.v)):
+            for (a, b), (a1, b1) in zip(mine, state[name]):
+                a.copy_(a1)
+                b.copy_(b1)
+        self.pow.copy_(state["pow"])
+
+
+class DdpgLearner(object):
+    """``policy``: an ``nn.Sequential`` (Linear, ReLU, ..., Linear, Tanh) and ``critic`` one without
+    the Tanh, as ``MlpActor.from_torch`` / ``MlpCritic.from_torch`` take them (or lists of
+    ``(W, b)`` tensors), on a GPU.  Their parameters are the float32 masters and are written in
+    place, so none may require grad (ValueError, as ``polyak_`` refuses such a target).
+
+    ``scale``: six floats; ``critic_step`` then feeds the critic ``actions / scale`` (one float32
+    division); None: the actions are normalised already.  ``max_batch``: the largest B of a step
+    (1..65 536); the workspace is sized for it once.  ``alloc(shape)``: the allocator of the
+    gradient and state tensors (default: ``torch.zeros`` on the networks' device; zeros are
+    required).
+
+    The constructor allocates ``actor_grads`` / ``critic_grads`` ([(gW, gb), ...], written whole by
+    every step), the Adam state and the workspace and builds every struct of the two C calls once; a
+    step checks its batch tensors and makes one call: two launches on the current stream (or
+    ``stream``), nothing allocated or read back, so both steps can be captured into a graph.  The
+    losses stay on the device (``critic_loss``, ``actor_loss``: 0-d tensors)."""
+
+    def __init__(self, policy, critic, scale=None, actor_lr=1e-4, critic_lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                 max_batch=256, alloc=None):
+        import torch
+        from . import _abi_ddpg
+        a_params, a_in, a_hidden = _masters(policy, True, "policy", (19, 20), 6,
+                                            "the policy's rows are obs_dim + 6 = 19 or 20 floats")
+        c_params, c_in, c_hidden = _masters(critic, False, "critic", (25, 26), 1,
+                                            "the critic's rows are obs_dim + 12 = 25 or 26 floats")
+        if a_in + 6 != c_in:
+            raise ValueError("the critic takes [row, action]: %d + 6 inputs, not %d" % (a_in, c_in))
+        self.device = device = a_params[0][0].device
+        if c_params[0][0].device != device:
+            raise ValueError("the critic is on %s, the policy on %s" % (c_params[0][0].device, device))
+        betas = (float(betas[0]), float(betas[1]))
+        for name, val in (("actor_lr", actor_lr), ("critic_lr", critic_lr), ("eps", eps)):
+            if not np.isfinite(float(val)):
+                raise ValueError(name + " must be finite")
+        if not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError("betas must be in [0, 1)")
+        if not float(eps) > 0.0:
+            raise ValueError("eps must be positive")
+        max_batch = int(max_batch)
+        if not 1 <= max_batch <= _abi_ddpg.CTR_DDPG_MAX_B:
+            raise ValueError("max_batch must be in 1..%d" % _abi_ddpg.CTR_DDPG_MAX_B)
+        if scale is not None:
+            scale = np.asarray(scale, dtype=np.float32).reshape(-1)
+            if scale.shape != (6,) or not np.isfinite(scale).all() or (scale == 0).any():
+                raise ValueError("scale is six finite, non-zero floats")
+        if device.type != "cuda":
+            raise ValueError("the networks are on %s: the learner's networks are on a GPU" % (device,))
+        if alloc is None:
+            def alloc(shape):
+                return torch.zeros(shape, dtype=torch.float32, device=device)
+        self._lib = lib = _abi.load()
+        self.max_batch = max_batch
+        self.in_dim = a_in
+        self._actor_struct = sa = _abi.CtrActor()
+        self._critic_struct = sc = _abi_critic.CtrCritic()
+        for s, in_dim, hidden in ((sa, a_in, a_hidden), (sc, c_in, c_hidden)):
+            s.in_dim, s.n_hidden = in_dim, len(hidden)
+            for l, w in enumerate(hidden):
+                s.width[l] = w
+        self._actor = _Net(a_params, alloc, actor_lr, betas, eps)
+        self._critic = _Net(c_params, alloc, critic_lr, betas, eps)
+        self.actor_grads, self.critic_grads = self._actor.grads, self._critic.grads
+        nbytes = int(lib.ctr_ddpg_workspace_bytes(sa, sc, max_batch))
+        if nbytes < 0:
+            raise _abi.CtrError("ctr_ddpg_workspace_bytes: " + lib.ctr_last_error().decode())
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        if self.workspace.data_ptr() % 16:
+            raise RuntimeError("workspace not 16-B aligned")
+        self.scale = None if scale is None else torch.from_numpy(scale).to(device)
+        self.critic_loss = torch.zeros((), dtype=torch.float32, device=device)
+        self.actor_loss = torch.zeros((), dtype=torch.float32, device=device)
+        # everything the two calls take but the batch and the stream, once
+        P = ctypes.c_void_p
+        self._ws, self._ws_bytes = P(self.workspace.data_ptr()), nbytes
+        self._scale_p = P(None if self.scale is None else self.scale.data_ptr())
+        self._closs, self._aloss = P(self.critic_loss.data_ptr()), P(self.actor_loss.data_ptr())
+        self._critic_step, self._actor_step = lib.ctr_ddpg_critic_step, lib.ctr_ddpg_actor_step
+        self._f32, self._index = torch.float32, device.index
+        self._raw_stream = torch._C._cuda_getCurrentRawStream
+
+    def _rows(self, t, cols, name):
+        if t.dtype is not self._f32 or t.device != self.device or t.dim() != 2 or t.shape[1] != cols \
+                or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 [B, %d] tensor on %s" % (name, cols, self.device))
+        B = t.shape[0]
+        if B > self.max_batch:
+            raise ValueError("B = %d rows, the learner was built for max_batch = %d" % (B, self.max_batch))
+        return B
+
+    def critic_step(self, rows, actions, target, stream=None):
+        """One regression step of the critic on ``target`` ([B] float32): rows [B, in_dim] as the
+        policy takes them, actions [B, 6] (divided by ``scale`` in the kernel when the learner has
+        one).  The loss goes to ``critic_loss``, the gradients to ``critic_grads``."""
+        B = self._rows(rows, self.in_dim, "rows")
+        if self._rows(actions, 6, "actions") != B:
+            raise ValueError("actions has another B than rows")
+        if target.dtype is not self._f32 or target.device != self.device or tuple(target.shape) != (B,) \
+                or not target.is_contiguous():
+            raise ValueError("target must be a contiguous float32 [B] tensor on %s" % (self.device,))
+        s = stream.cuda_stream if stream is not None else self._raw_stream(self._index)
+        c = self._critic
+        rc = self._critic_step(self._critic_struct, c.struct, c.adam, rows.data_ptr(), actions.data_ptr(), self._scale_p,
+                               target.data_ptr(), B, self._closs, self._ws, self._ws_bytes, s)
+        if rc:
+            _abi.check(rc, "ctr_ddpg_critic_step")
+
+    def actor_step(self, rows, stream=None):
+        """One step of the policy up Q(row, pi(row)) under the critic's current parameters, which
+        are only read.  The loss (-mean Q) goes to ``actor_loss``, the gradients to ``actor_grads``."""
+        B = self._rows(rows, self.in_dim, "rows")
+        s = stream.cuda_stream if stream is not None else self._raw_stream(self._index)
+        a, c = self._actor, self._critic
+        rc = self._actor_step(self._actor_struct, a.struct, a.adam, self._critic_struct, c.arrays["W"], c.arrays["b"],
+                              rows.data_ptr(), B, self._aloss, self._ws, self._ws_bytes, s)
+        if rc:
+            _abi.check(rc, "ctr_ddpg_actor_step")
+
+    def state_dict(self):
+        """Adam's state of both networks, cloned: {"actor": {"m", "v", "pow"}, "critic": {...}} with
+        ``m`` and ``v`` as [(W-shaped, b-shaped), ...] and ``pow`` = [beta1^t, beta2^t]."""
+        return {"actor": self._actor.state(), "critic": self._critic.state()}
+
+    def load_state_dict(self, state):
+        """Copies a ``state_dict()`` into the learner's own tensors (the device pointers stay)."""
+        self._actor.load_state(state["actor"])
+        self._critic.load_state(state["critic"])

@@ -773,6 +773,74 @@ typedef struct ctr_polyak_net_t {
 } ctr_polyak_net_t;
 int ctr_polyak(const ctr_polyak_net_t *nets, int32_t n_nets, float tau, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * DDPG's two updates on the learner's float32 parameters (added within ABI 17: new symbols, no
+ * entry point or struct changes).  The networks are the actor's and the critic's shapes ("MLP
+ * actor", "MLP critic" above: only in_dim, n_hidden and width are read; scale and blob are not),
+ * but here every value is float32: relu(z) = z > 0 ? z : 0 between the layers, the products on the
+ * f32-in / f32-accumulate matrix instructions (chains of fmaf in a fixed order).
+ *
+ * ctr_ddpg_critic_step: rows [B][in_dim - 6], actions [B][6], target [B] (device).  With scale
+ * (device [6]) the critic sees actions[i][j] / scale[j], one f32 division; NULL: the actions are
+ * normalised already.
+ *     q_i = Q([row_i, a_i]);  loss = sum_i (q_i - target_i)^2 * (1/B);  dL/dq_i = (q_i - target_i) * (2/B)
+ * ctr_ddpg_actor_step: rows [B][in_dim] of the actor (device); critic_W / critic_b the critic's
+ * current float32 parameters (device, [n_hidden + 1] layers), read only.
+ *     a_i = (float)tanh(policy logits);  q_i = Q([row_i, a_i]);  loss = sum_i q_i * (-1/B);  dL/dq_i = -1/B
+ * and backward through the critic to its six action inputs only, through 1 - a^2, through the policy
+ * (actor->scale is not read).
+ * Either call writes the gradient of every W[l], b[l] of its network whole to gW[l], gb[l], the
+ * loss to *loss (device, or NULL), and then makes one Adam step on W, b in place with the state mW,
+ * mb, vW, vb (every tensor of its parameter's shape) and pow = {beta1^t, beta2^t} (device float[2],
+ * {1, 1} before the first step), every operation rounded to f32, no fused multiply-add, division
+ * and sqrtf correctly rounded:
+ *     pow1' = pow1 * beta1;  pow2' = pow2 * beta2
+ *     m' = (beta1 * m) + ((1 - beta1) * g)
+ *     v' = (beta2 * v) + (((1 - beta2) * g) * g)
+ *     p' = p - lr * ((m' / (1 - pow1')) / (sqrtf(v' / (1 - pow2')) + eps))
+ * so a float32 restatement in numpy of the step from the stored gradients gives the same bits.
+ *
+ * Two launches on `stream`: the first takes tiles of 16 rows, one workgroup per slot (at most 64
+ * slots; slot s takes tiles s, s + slots, ...), keeps a tile's activations in LDS between forward
+ * and backward and sums its tiles' gradients into its slot of the workspace; it also advances pow
+ * into the workspace.  The second sums the slots in slot order per parameter, stores the gradient,
+ * applies Adam with the advanced pow and stores that to pow.  No atomics, no workgroup waits for
+ * another, the order of every sum depends on the shapes and B only: the same inputs give the same
+ * bits.  (The two sums over rows whose terms cancel, the loss and the bias gradients, and the
+ * policy's tanh run in f64 and are rounded to f32 once; everything else is f32.)  Nothing is allocated or read back; both
+ * calls can be captured into a graph.  Every shape
+ * that ctr_actor / ctr_critic accept fits (107 KB of LDS for the widest actor with the widest
+ * critic).  B is 1..65 536; B = 0 is a no-op.
+ * workspace: device, 16-B aligned, ctr_ddpg_workspace_bytes(actor, critic, max_B) bytes serve both
+ * calls for every B <= max_B (-1 on a refused shape or max_B outside 1..65 536); the calls may
+ * share it (they are stream-ordered).
+ * Refused (CTR_EINVAL, before any HIP call, ctr_last_error names the function): a NULL struct; a
+ * shape ctr_actor / ctr_critic refuse; actor->in_dim + 6 != critic->in_dim; a NULL pointer array,
+ * pow or layer in 0..n_hidden; a gradient or state tensor (or pow) that is a parameter tensor;
+ * workspace NULL, misaligned or too small for B; lr, beta1, beta2 or eps not finite; a beta
+ * outside [0, 1); eps <= 0; B outside 0..65 536; a NULL batch array where B > 0. */
+typedef struct ctr_ddpg_net_t {
+    float *const *W;                /* parameters (the f32 masters), device, [n_hidden + 1]  */
+    float *const *b;                /* layers, updated in place                              */
+    float *const *gW;               /* gradients, written whole                              */
+    float *const *gb;
+    float *const *mW;               /* Adam's first moments                                  */
+    float *const *mb;
+    float *const *vW;               /* Adam's second moments                                 */
+    float *const *vb;
+    float *pow;                     /* device float[2]: beta1^t, beta2^t                     */
+} ctr_ddpg_net_t;
+typedef struct ctr_ddpg_adam_t {
+    float lr, beta1, beta2, eps;
+} ctr_ddpg_adam_t;
+int64_t ctr_ddpg_workspace_bytes(const ctr_actor_t *actor, const ctr_critic_t *critic, int64_t max_B);
+int ctr_ddpg_critic_step(const ctr_critic_t *critic, const ctr_ddpg_net_t *net, const ctr_ddpg_adam_t *adam,
+                         const float *rows, const float *actions, const float *scale, const float *target, int64_t B,
+                         float *loss, void *workspace, int64_t workspace_bytes, void *stream);
+int ctr_ddpg_actor_step(const ctr_actor_t *actor, const ctr_ddpg_net_t *net, const ctr_ddpg_adam_t *adam,
+                        const ctr_critic_t *critic, const float *const *critic_W, const float *const *critic_b,
+                        const float *rows, int64_t B, float *loss, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* CtrReachEnv.reset for the environments with mask[i] != 0 (mask NULL = all).
  * goal [n][3] or NULL (sample a goal), system [n] or NULL (sample uniformly).
  * Writes the reset observation to obs [n][obs_dim]. */
