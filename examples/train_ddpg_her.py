@@ -44,9 +44,19 @@ through both, Adam), two launches each, in float32 on those parameters in place.
 ``sample_td``, ``critic_step``, ``actor_step`` and ``polyak_``, none of it autograd; the action is
 divided by ``scale`` inside ``critic_step``.  The modules still own the parameters.
 
+With ``--td3`` (``main(..., td3=True)``, which implies ``--device-update``) the same loop trains TD3
+(Fujimoto et al. 2018) instead of DDPG: a second critic with its target and its ``MlpCritic``, the
+target from the smaller of the two target critics on a noise-smoothed target action
+(``her.sample_td3(batch_size, actor_targ, critic_targ_dev, critic2_targ_dev, gamma, TARGET_NOISE,
+NOISE_CLIP)``, still one launch behind the sampler's scans), both critics regressed on it by one
+``Td3Learner.critic_step`` (two launches), and on every ``POLICY_DELAY``-th update the policy's step
+under critic 1 and one ``polyak_`` of the three target networks.  ``TARGET_NOISE`` 0.2, ``NOISE_CLIP``
+0.5 and ``POLICY_DELAY`` 2 are TD3's published defaults and stable-baselines'.  The critic loss
+reported is the mean of the two critics'.
+
 usage: python examples/train_ddpg_her.py [--num-envs N] [--iterations I] [--steps-per-iter S]
            [--batch-size B] [--updates-per-iter U] [--hidden 64,64] [--seed 0] [--device cuda]
-           [--device-targets] [--device-polyak] [--device-update]"""
+           [--device-targets] [--device-polyak] [--device-update] [--td3]"""
 import argparse
 import os
 import sys
@@ -58,12 +68,13 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-ctr-reach_amd"))
 from ctr_reach_amd import CtrReachVecEnv  # noqa: E402
-from ctr_reach_amd.learner import DdpgLearner  # noqa: E402
+from ctr_reach_amd.learner import DdpgLearner, Td3Learner  # noqa: E402
 from ctr_reach_amd.policy import ExploreNoise, MlpActor, MlpCritic, polyak_  # noqa: E402
 
 GAMMA, TAU, ACTOR_LR, CRITIC_LR = 0.99, 0.001, 1e-4, 1e-3
 N_SAMPLED_GOAL, STRATEGY = 4, "future"
 SIGMA, RANDOM_EPS = 0.2, 0.3
+TARGET_NOISE, NOISE_CLIP, POLICY_DELAY = 0.2, 0.5, 2                         # TD3 (--td3)
 
 
 def mlp(n_in, hidden, n_out, tanh):
@@ -78,8 +89,9 @@ def mlp(n_in, hidden, n_out, tanh):
 
 
 def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, updates_per_iter=40, hidden=(64, 64), seed=0,
-         device="cuda", device_targets=False, device_polyak=False, device_update=False):
+         device="cuda", device_targets=False, device_polyak=False, device_update=False, td3=False):
     device = torch.device(device)
+    device_update = device_update or td3
     device_polyak = device_polyak or device_update
     device_targets = device_targets or device_polyak
     torch.manual_seed(seed)
@@ -98,8 +110,18 @@ def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, update
     critic_targ.load_state_dict(critic.state_dict())
     for p in list(policy_targ.parameters()) + list(critic_targ.parameters()):
         p.requires_grad_(False)
+    critic2 = critic2_targ = critic2_targ_dev = None
+    if td3:                                                                  # the twin critic and its target
+        critic2 = mlp(d + 6, hidden, 1, False).to(device).requires_grad_(False)
+        critic2_targ = mlp(d + 6, hidden, 1, False).to(device).requires_grad_(False)
+        critic2_targ.load_state_dict(critic2.state_dict())
     learner = None
-    if device_update:                                                        # the masters are written by the kernels
+    if td3:
+        policy.requires_grad_(False)
+        critic.requires_grad_(False)
+        learner = Td3Learner(policy, critic, critic2, scale=venv.action_space.high, actor_lr=ACTOR_LR, critic_lr=CRITIC_LR,
+                             max_batch=batch_size)
+    elif device_update:                                                        # the masters are written by the kernels
         policy.requires_grad_(False)
         critic.requires_grad_(False)
         learner = DdpgLearner(policy, critic, scale=venv.action_space.high, actor_lr=ACTOR_LR, critic_lr=CRITIC_LR,
@@ -114,12 +136,29 @@ def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, update
     if device_targets:                                                       # the targets' bf16 view, once
         actor_targ = MlpActor.from_torch(policy_targ, venv.action_space.high, device)
         critic_targ_dev = MlpCritic.from_torch(critic_targ, device)
+    if td3:
+        critic2_targ_dev = MlpCritic.from_torch(critic2_targ, device)
     losses = []
+    updates = 0
     for it in range(iterations):
         venv.collect(actor, steps_per_iter, noise)
         critic_sum = torch.zeros((), device=device)
         policy_sum = torch.zeros((), device=device)
+        policy_updates = 0
         for _ in range(updates_per_iter):
+            if td3:                                                          # sample_td3, the twin step; every 2nd: the rest
+                batch = her.sample_td3(batch_size, actor_targ, critic_targ_dev, critic2_targ_dev, GAMMA, TARGET_NOISE,
+                                       NOISE_CLIP)
+                learner.critic_step(batch["obs"], batch["action"], batch["target"])
+                critic_sum += learner.critic_loss.mean()
+                updates += 1
+                if updates % POLICY_DELAY == 0:
+                    learner.actor_step(batch["obs"])
+                    polyak_([(actor_targ, policy, policy_targ), (critic_targ_dev, critic, critic_targ),
+                             (critic2_targ_dev, critic2, critic2_targ)], TAU)
+                    policy_sum += learner.actor_loss
+                    policy_updates += 1
+                continue
             if device_update:                                                # sample_td, two steps, polyak_: no autograd
                 batch = her.sample_td(batch_size, actor_targ, critic_targ_dev, GAMMA)
                 learner.critic_step(batch["obs"], batch["action"], batch["target"])
@@ -159,8 +198,10 @@ def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, update
             policy_sum += policy_loss.detach()
         actor.load_(policy)
         # the iteration's only host read
-        losses.append((critic_sum.item() / max(updates_per_iter, 1), policy_sum.item() / max(updates_per_iter, 1)))
-    return dict(actor=actor, policy=policy, critic=critic, policy_targ=policy_targ, critic_targ=critic_targ,
+        losses.append((critic_sum.item() / max(updates_per_iter, 1),
+                       policy_sum.item() / max(policy_updates if td3 else updates_per_iter, 1)))
+    return dict(critic2=critic2, critic2_targ=critic2_targ, critic2_targ_dev=critic2_targ_dev,
+                actor=actor, policy=policy, critic=critic, policy_targ=policy_targ, critic_targ=critic_targ,
                 actor_targ=actor_targ, critic_targ_dev=critic_targ_dev, learner=learner, losses=losses,
                 rollout_stats=venv.rollout_stats, venv=venv, her=her)
 
@@ -180,10 +221,12 @@ if __name__ == "__main__":
                     help="the Polyak update and both blob refreshes in one polyak_ launch (implies --device-targets)")
     ap.add_argument("--device-update", action="store_true",
                     help="the critic's and the policy's updates from a DdpgLearner, no autograd (implies --device-polyak)")
+    ap.add_argument("--td3", action="store_true",
+                    help="TD3: twin critics, smoothed clipped double-Q targets, delayed policy updates (implies --device-update)")
     args = ap.parse_args()
     out = main(args.num_envs, args.iterations, args.steps_per_iter, args.batch_size, args.updates_per_iter,
                tuple(int(w) for w in args.hidden.split(",")), args.seed, args.device, args.device_targets,
-               args.device_polyak, args.device_update)
+               args.device_polyak, args.device_update, args.td3)
     for it, (c, p) in enumerate(out["losses"]):
         print("iteration %3d: critic loss %.4g, policy loss %.4g" % (it, c, p))
     stats = out["rollout_stats"]

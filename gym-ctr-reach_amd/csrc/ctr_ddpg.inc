@@ -13,6 +13,10 @@
 // gradient and makes the Adam step.  No atomics, nobody waits for anybody, and the order of every
 // sum is a function of the shapes and B alone.
 //
+// ctr_td3_critic_step makes the critic's step for TD3's two critics in the same two launches: the
+// grids get a second dimension, plane blockIdx.y works on critic y with its own arguments and its
+// own region of the workspace, and the kernels' bodies are device functions both pairs call.
+//
 // The products run on v_mfma_f32_16x16x4_f32 (f32 in, f32 accumulate: a chain of fmaf at exact
 // f32).  Lane (c = lane & 15, g = lane >> 4) gives A[i = c][k = g] and B[k = g][j = c] and holds
 // D[i = 4 g + reg][j = c].  A k-block of 16 is four MFMAs; in MFMA t lane group g supplies
@@ -266,10 +270,10 @@ struct DdpgGradK {
     char *ws;
 };
 
+// The gradient launch's work of one workgroup (slot blockIdx.x of k.ws); s_loss: DDPG_T floats of LDS.
 template <bool ACTOR>
-__global__ __launch_bounds__(BLOCK) void k_ddpg_grad(DdpgGradK k)
+__device__ __forceinline__ void ddpg_grad_block(const DdpgGradK &k, float *s_loss)
 {
-    __shared__ float s_loss[DDPG_T];
     float *lds = reinterpret_cast<float *>(actor_lds_base(0));
     DdpgLds La = {}, Lc = {};
     if (ACTOR) lds = ddpg_lds_net(k.net, lds, La);
@@ -348,6 +352,23 @@ __global__ __launch_bounds__(BLOCK) void k_ddpg_grad(DdpgGradK k)
     if (threadIdx.x == 0) reinterpret_cast<double *>(k.ws + 16)[blockIdx.x] = lsum;
 }
 
+template <bool ACTOR>
+__global__ __launch_bounds__(BLOCK) void k_ddpg_grad(DdpgGradK k)
+{
+    __shared__ float s_loss[DDPG_T];
+    ddpg_grad_block<ACTOR>(k, s_loss);
+}
+
+// TD3's two critics in one launch: plane blockIdx.y of the grid is k_ddpg_grad<false> on critic y,
+// with its own arguments and its own region of the workspace.  The branch is wave-uniform, and each
+// side reads its struct by constant offsets.
+__global__ __launch_bounds__(BLOCK) void k_td3_grad(DdpgGradK k0, DdpgGradK k1)
+{
+    __shared__ float s_loss[DDPG_T];
+    if (blockIdx.y == 0) ddpg_grad_block<false>(k0, s_loss);
+    else ddpg_grad_block<false>(k1, s_loss);
+}
+
 struct DdpgApplyK {
     int32_t params, biases, slots;
     int32_t end[DDPG_TENSORS];         // the flat order's tensor ends (past the network: params)
@@ -375,7 +396,8 @@ __device__ __forceinline__ float ddpg_adam(float p, float g, float &m, float &v,
     return p - step;
 }
 
-__global__ __launch_bounds__(BLOCK) void k_ddpg_apply(DdpgApplyK k)
+// The apply launch's work of one thread: element blockIdx.x * BLOCK + threadIdx.x of k's network.
+__device__ __forceinline__ void ddpg_apply_element(const DdpgApplyK &k)
 {
     const float *hdr = reinterpret_cast<const float *>(k.ws);
     const float *part = reinterpret_cast<const float *>(k.ws + DDPG_HDR);
@@ -427,6 +449,16 @@ __global__ __launch_bounds__(BLOCK) void k_ddpg_apply(DdpgApplyK k)
     p[i] = ddpg_adam(p[i], g, m, v, k.lr, k.beta1, k.beta2, k.eps, pw1, pw2);
     mp[i] = m;
     vp[i] = v;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_ddpg_apply(DdpgApplyK k) { ddpg_apply_element(k); }
+
+// k_ddpg_apply on TD3's two critics: plane blockIdx.y applies critic y's slots (the grid's x is the
+// larger network's; the threads past a network's parameters leave as in k_ddpg_apply).
+__global__ __launch_bounds__(BLOCK) void k_td3_apply(DdpgApplyK k0, DdpgApplyK k1)
+{
+    if (blockIdx.y == 0) ddpg_apply_element(k0);
+    else ddpg_apply_element(k1);
 }
 
 int ddpg_fail(const char *fn, const char *why)
@@ -612,6 +644,82 @@ int ctr_ddpg_actor_step(const ctr_actor_t *actor, const ctr_ddpg_net_t *net, con
     ap.loss_scale = -1.0 / (double)B;
     ap.loss = loss;
     return ddpg_launch<true>(fn, gk, ap, stream);
+}
+
+int64_t ctr_td3_workspace_bytes(const ctr_actor_t *actor, const ctr_critic_t *critic1, const ctr_critic_t *critic2,
+                                int64_t max_B)
+{
+    const char *fn = "ctr_td3_workspace_bytes";
+    DdpgNetK an, c1, c2;
+    if (ddpg_shape_check(fn, actor, critic1, true, &an, &c1)) return -1;
+    if (ddpg_shape_check(fn, actor, critic2, true, &an, &c2)) return -1;
+    if (max_B < 1 || max_B > DDPG_MAX_B) {
+        ddpg_fail(fn, "max_B must be in 1..65536");
+        return -1;
+    }
+    // the two critics' regions, one behind the other (each a multiple of 16 B); or the actor's step
+    const int64_t twin = ddpg_ws_bytes(c1.params, c1.biases, max_B) + ddpg_ws_bytes(c2.params, c2.biases, max_B);
+    return std::max(twin, ddpg_ws_bytes(an.params, an.biases, max_B));
+}
+
+int ctr_td3_critic_step(const ctr_critic_t *const critic[2], const ctr_ddpg_net_t *const net[2],
+                        const ctr_ddpg_adam_t *adam, const float *rows, const float *actions, const float *scale,
+                        const float *target, int64_t B, float *loss, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const char *fn = "ctr_td3_critic_step";
+    DdpgGradK gk[2] = {};
+    DdpgApplyK ap[2];
+    if (!critic || !net) return ddpg_fail(fn, "critic or net is NULL");
+    if (!critic[0] || !critic[1] || !net[0] || !net[1]) return ddpg_fail(fn, "NULL entry in critic[2] or net[2]");
+    if (int r = ddpg_shape_check(fn, nullptr, critic[0], false, nullptr, &gk[0].net)) return r;
+    if (int r = ddpg_shape_check(fn, nullptr, critic[1], false, nullptr, &gk[1].net)) return r;
+    if (gk[0].net.in_dim != gk[1].net.in_dim) return ddpg_fail(fn, "the two critics must have the same in_dim");
+    // critic 0's region as ctr_ddpg_critic_step lays it out, critic 1's behind it (a region is a multiple of 16 B)
+    static_assert(DDPG_HDR % 16 == 0, "a region is a multiple of 16 B");
+    const int64_t Bc = B < 0 ? 0 : std::min(B, DDPG_MAX_B);
+    const int64_t off = ddpg_ws_bytes(gk[0].net.params, gk[0].net.biases, Bc);
+    if (int r = ddpg_learn_check(fn, net[0], adam, B, workspace, workspace_bytes, &gk[0].net, &ap[0])) return r;
+    if (workspace_bytes < off + ddpg_ws_bytes(gk[1].net.params, gk[1].net.biases, Bc))
+        return ddpg_fail(fn, "workspace too small (ctr_td3_workspace_bytes)");
+    if (int r = ddpg_learn_check(fn, net[1], adam, B, static_cast<char *>(workspace) + off, workspace_bytes - off,
+                                 &gk[1].net, &ap[1]))
+        return r;
+    // the planes run side by side: nothing one of them writes may belong to the other
+    const int nt0 = 2 * (gk[0].net.n_hidden + 1), nt1 = 2 * (gk[1].net.n_hidden + 1);
+    if (ap[0].pow == ap[1].pow) return ddpg_fail(fn, "the two nets share a tensor (pow)");
+    for (int t = 0; t < nt0; ++t) {
+        const float *const mine[4] = {ap[0].p[t], ap[0].g[t], ap[0].m[t], ap[0].v[t]};
+        for (int u = 0; u < nt1; ++u) {
+            const float *const theirs[4] = {ap[1].p[u], ap[1].g[u], ap[1].m[u], ap[1].v[u]};
+            for (int i = 0; i < 4; ++i)
+                for (int j = 0; j < 4; ++j)
+                    if (mine[i] == theirs[j] || mine[i] == ap[1].pow || theirs[j] == ap[0].pow)
+                        return ddpg_fail(fn, "the two nets share a parameter, gradient or state tensor");
+        }
+    }
+    if (B > 0 && (!rows || !actions || !target)) return ddpg_fail(fn, "rows, actions or target is NULL");
+    if (B == 0) return 0;
+    size_t shm = 0;
+    for (int y = 0; y < 2; ++y) {
+        gk[y].rows = rows;
+        gk[y].actions = actions;
+        gk[y].scale = scale;
+        gk[y].target = target;
+        gk[y].B = (int32_t)B;
+        gk[y].dq = (float)(2.0 / (double)B);
+        gk[y].beta1 = ap[y].beta1;
+        gk[y].beta2 = ap[y].beta2;
+        gk[y].pow = ap[y].pow;
+        gk[y].ws = const_cast<char *>(ap[y].ws);
+        ap[y].loss_scale = 1.0 / (double)B;
+        ap[y].loss = loss ? loss + y : nullptr;
+        shm = std::max(shm, ddpg_lds_floats(gk[y].net) * sizeof(float) + ACTOR_LDS_SLACK);
+    }
+    if (int r = allow_dynamic_lds(k_td3_grad, shm)) return r;
+    const unsigned gx = grid_for(std::max(ap[0].params, ap[1].params));
+    hipLaunchKernelGGL(k_td3_grad, dim3((unsigned)ap[0].slots, 2), dim3(BLOCK), shm, (hipStream_t)stream, gk[0], gk[1]);
+    hipLaunchKernelGGL(k_td3_apply, dim3(gx, 2), dim3(BLOCK), 0, (hipStream_t)stream, ap[0], ap[1]);
+    return hip_check("ctr_td3_critic_step launch");
 }
 
 }  // extern "C"

@@ -28,6 +28,11 @@
 //                 f32 matrix instructions, the weight gradients summed per workgroup into workspace slots;
 //   k_ddpg_apply  the slots summed per parameter, the gradient stored and one Adam step made
 //                 (ctr_ddpg_critic_step, ctr_ddpg_actor_step; ctr_ddpg.inc)
+//   k_her_sample_td3  k_her_sample_td for TD3: the target action smoothed by clipped Gaussian noise, two
+//                 target critics one after the other in the same LDS region, the smaller q in the target
+//                 (ctr_her_sample_td3; ctr_critic.inc)
+//   k_td3_grad, k_td3_apply  k_ddpg_grad<false> and k_ddpg_apply on TD3's two critics at once, plane
+//                 blockIdx.y of the grid on critic y (ctr_td3_critic_step; ctr_ddpg.inc)
 //   k_collect     k_rollout with exploration noise on each action and each step recorded into the HER
 //                 store (ctr_collect, at the end of the file)
 //   k_explore     the exploration noise alone, one env per lane (ctr_explore; explore_lane, ctr_device.hpp)

@@ -10,6 +10,7 @@ with the environments stepped in lockstep by hand-written HIP kernels on gfx950.
   HerReplayBuffer  device HER replay feed (stable-baselines 2 'future' relabelling)
   MlpActor         the policy's actor, run by hand-written kernels (rollout, collect, follow)
   DdpgLearner      DDPG's critic and actor updates (forward, backward, Adam) on the device
+  Td3Learner       the same with TD3's twin critics, both regressed in one pair of launches
   paths            line / circle / helix waypoint paths for follow() and dls_ik_path
 """
 from .vec_env import CtrReachVecEnv, FollowResult  # noqa: F401
@@ -18,7 +19,7 @@ from .systems import Tube, default_kwargs, default_systems_parameters  # noqa: F
 from .goal_tolerance import GoalTolerance  # noqa: F401
 from .ik import dls_ik_path, dls_ik_position_only  # noqa: F401
 from .her import HerReplayBuffer  # noqa: F401
-from .policy import MlpActor, MlpCritic, polyak_  # noqa: F401
-from .learner import DdpgLearner  # noqa: F401
+from .policy import MlpActor, MlpCritic, TargetSmoothing, polyak_  # noqa: F401
+from .learner import DdpgLearner, Td3Learner  # noqa: F401
 from .paths import circle_path, helix_path, line_path  # noqa: F401
 from . import paths  # noqa: F401

@@ -174,3 +174,49 @@ class HerReplayBuffer(object):
         _abi.check(rc, "ctr_her_sample_td")
         self._counter += 1
         return out
+
+    def sample_td3(self, batch_size, actor, critic1, critic2, gamma, sigma=0.2, clip=0.5, seed=None, stream=None,
+                   return_index=False, return_next=False):
+        """``sample`` with the TD3 target of the drawn rows (ctr_her_sample_td3): ``sample_td``'s dict,
+        with target [B] = reward + gamma * (1 - done) * min(Q1', Q2')(next_obs, a'') from the target
+        policy ``actor`` and the two target critics (``MlpCritic``; they may be the same object), all
+        on this buffer's device.  a'' = clip(pi'(next_obs) + clip(sigma * z, -clip, clip), -1, 1) is
+        the smoothed target action in the normalised box: z a standard Gaussian keyed by (seed,
+        counter, row) (``policy.TargetSmoothing`` restates it), ``sigma`` >= 0 its std (0: no noise,
+        nothing drawn) and ``clip`` >= 0 its bound (``inf``: none).  With ``return_next`` also
+        q1_next [B], q2_next [B] and next_action [B, 6] = a''.  One draw: the counter advances as in
+        ``sample``.  Asynchronous."""
+        from . import _abi_td3
+        dev = self.venv.device
+        for net, name in ((actor, "actor"), (critic1, "critic1"), (critic2, "critic2")):
+            if getattr(net, "blob", None) is None:
+                raise ValueError("sample_td3: the %s must be on the device" % name)
+            if net.device.type != dev.type or (None not in (net.device.index, dev.index)
+                                               and net.device.index != dev.index):
+                raise ValueError("sample_td3: the %s is on %s, the buffer on %s" % (name, net.device, dev))
+        gamma, sigma, clip = float(gamma), float(sigma), float(clip)
+        if not np.isfinite(gamma):
+            raise ValueError("sample_td3: gamma must be finite")
+        if not (np.isfinite(sigma) and sigma >= 0.0):
+            raise ValueError("sample_td3: sigma must be finite and >= 0")
+        if not clip >= 0.0:
+            raise ValueError("sample_td3: clip must be >= 0 (inf: the noise is not clipped)")
+        torch = _torch()
+        B, out, hb = self._batch(batch_size, return_index)
+        out["target"] = torch.empty(B, dtype=torch.float32, device=dev)
+        if return_next:
+            out["q1_next"] = torch.empty(B, dtype=torch.float32, device=dev)
+            out["q2_next"] = torch.empty(B, dtype=torch.float32, device=dev)
+            out["next_action"] = torch.empty((B, 6), dtype=torch.float32, device=dev)
+        td = _abi_td3.CtrHerTd3()
+        td.actor, td.critic1, td.critic2 = (ctypes.pointer(actor._struct), ctypes.pointer(critic1._struct),
+                                            ctypes.pointer(critic2._struct))
+        td.gamma, td.sigma, td.clip = gamma, sigma, clip
+        td.target, td.q1_next, td.q2_next, td.next_action = (_abi.ptr(out["target"]), _abi.ptr(out.get("q1_next")),
+                                                             _abi.ptr(out.get("q2_next")),
+                                                             _abi.ptr(out.get("next_action")))
+        rc = self.lib.ctr_her_sample_td3(self._h, B, self._draw_seed(seed), self._counter, hb, td,
+                                         _abi.stream_ptr(stream, self.venv.device.index))
+        _abi.check(rc, "ctr_her_sample_td3")
+        self._counter += 1
+        return out

@@ -9,7 +9,9 @@ parameters.  No autograd and no torch optimiser:
     learner.actor_step(batch["obs"])
     polyak_([(actor_targ, policy, policy_targ), (critic_targ_dev, critic, critic_targ)], 0.001)
 
-``adam_reference`` is the numpy float32 restatement of the Adam step (the kernel gives its bits).
+``Td3Learner`` is the same learner with TD3's two critics, both regressed by one call
+(ctr_td3_critic_step).  ``adam_reference`` is the numpy float32 restatement of the Adam step (the
+kernel gives its bits).
 """
 import ctypes
 
@@ -262,3 +264,138 @@ class DdpgLearner(object):
         """Copies a ``state_dict()`` into the learner's own tensors (the device pointers stay)."""
         self._actor.load_state(state["actor"])
         self._critic.load_state(state["critic"])
+
+
+class Td3Learner(object):
+    """``DdpgLearner`` with TD3's twin critics (ctr_td3_critic_step): ``policy`` and two critics
+    ``critic1``, ``critic2`` of one input width (their hidden layers may differ), given as
+    ``DdpgLearner`` takes its networks.  The two critics may share no tensor.
+
+        learner = Td3Learner(policy, critic1, critic2, scale=venv.action_space.high)
+        batch = buf.sample_td3(256, actor_targ, critic1_targ, critic2_targ, gamma, sigma=0.2, clip=0.5)
+        learner.critic_step(batch["obs"], batch["action"], batch["target"])
+        if update % 2 == 0:                                  # TD3's delayed policy and target updates
+            learner.actor_step(batch["obs"])
+            polyak_([(actor_targ, policy, policy_targ), (critic1_targ_dev, critic1, critic1_targ),
+                     (critic2_targ_dev, critic2, critic2_targ)], 0.005)
+
+    ``critic_step`` regresses both critics on the one target in one call: two launches, whose second
+    grid dimension is the critic, each critic's bits those of ``DdpgLearner.critic_step`` on it.
+    ``actor_step`` is ``DdpgLearner``'s under critic 1 (TD3 ascends Q1).  ``critic_lr`` serves both
+    critics.  The constructor builds every struct of the two C calls once; ``critic_grads`` is the
+    pair of the critics' gradient lists, ``critic_loss`` a device tensor [2], ``actor_loss`` 0-d."""
+
+    def __init__(self, policy, critic1, critic2, scale=None, actor_lr=1e-4, critic_lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                 max_batch=256, alloc=None):
+        import torch
+        from . import _abi_ddpg, _abi_td3
+        a_params, a_in, a_hidden = _masters(policy, True, "policy", (19, 20), 6,
+                                            "the policy's rows are obs_dim + 6 = 19 or 20 floats")
+        c_nets = []
+        for critic, name in ((critic1, "critic1"), (critic2, "critic2")):
+            c_params, c_in, c_hidden = _masters(critic, False, name, (25, 26), 1,
+                                                "the %s's rows are obs_dim + 12 = 25 or 26 floats" % name)
+            if a_in + 6 != c_in:
+                raise ValueError("the %s takes [row, action]: %d + 6 inputs, not %d" % (name, a_in, c_in))
+            c_nets.append((c_params, c_in, c_hidden))
+        self.device = device = a_params[0][0].device
+        for (c_params, _, _), name in zip(c_nets, ("critic1", "critic2")):
+            if c_params[0][0].device != device:
+                raise ValueError("the %s is on %s, the policy on %s" % (name, c_params[0][0].device, device))
+        if any(t1 is t2 or (t1.numel() and t1.data_ptr() == t2.data_ptr())
+               for p1 in c_nets[0][0] for t1 in p1 for p2 in c_nets[1][0] for t2 in p2):
+            raise ValueError("critic1 and critic2 share a tensor: the twin step updates them side by side")
+        betas = (float(betas[0]), float(betas[1]))
+        for name, val in (("actor_lr", actor_lr), ("critic_lr", critic_lr), ("eps", eps)):
+            if not np.isfinite(float(val)):
+                raise ValueError(name + " must be finite")
+        if not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError("betas must be in [0, 1)")
+        if not float(eps) > 0.0:
+            raise ValueError("eps must be positive")
+        max_batch = int(max_batch)
+        if not 1 <= max_batch <= _abi_ddpg.CTR_DDPG_MAX_B:
+            raise ValueError("max_batch must be in 1..%d" % _abi_ddpg.CTR_DDPG_MAX_B)
+        if scale is not None:
+            scale = np.asarray(scale, dtype=np.float32).reshape(-1)
+            if scale.shape != (6,) or not np.isfinite(scale).all() or (scale == 0).any():
+                raise ValueError("scale is six finite, non-zero floats")
+        if device.type != "cuda":
+            raise ValueError("the networks are on %s: the learner's networks are on a GPU" % (device,))
+        if alloc is None:
+            def alloc(shape):
+                return torch.zeros(shape, dtype=torch.float32, device=device)
+        self._lib = lib = _abi.load()
+        self.max_batch = max_batch
+        self.in_dim = a_in
+        self._actor_struct = sa = _abi.CtrActor()
+        self._critic_structs = sc = (_abi_critic.CtrCritic(), _abi_critic.CtrCritic())
+        for s, in_dim, hidden in ((sa, a_in, a_hidden), (sc[0],) + c_nets[0][1:], (sc[1],) + c_nets[1][1:]):
+            s.in_dim, s.n_hidden = in_dim, len(hidden)
+            for l, w in enumerate(hidden):
+                s.width[l] = w
+        self._actor = _Net(a_params, alloc, actor_lr, betas, eps)
+        self._critics = (_Net(c_nets[0][0], alloc, critic_lr, betas, eps), _Net(c_nets[1][0], alloc, critic_lr, betas, eps))
+        self.actor_grads = self._actor.grads
+        self.critic_grads = (self._critics[0].grads, self._critics[1].grads)
+        nbytes = int(lib.ctr_td3_workspace_bytes(sa, sc[0], sc[1], max_batch))
+        if nbytes < 0:
+            raise _abi.CtrError("ctr_td3_workspace_bytes: " + lib.ctr_last_error().decode())
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        if self.workspace.data_ptr() % 16:
+            raise RuntimeError("workspace not 16-B aligned")
+        self.scale = None if scale is None else torch.from_numpy(scale).to(device)
+        self.critic_loss = torch.zeros(2, dtype=torch.float32, device=device)
+        self.actor_loss = torch.zeros((), dtype=torch.float32, device=device)
+        # everything the two calls take but the batch and the stream, once
+        P = ctypes.c_void_p
+        self._critic_pair = _abi_td3.CriticPair(ctypes.pointer(sc[0]), ctypes.pointer(sc[1]))
+        self._net_pair = _abi_td3.NetPair(ctypes.pointer(self._critics[0].struct), ctypes.pointer(self._critics[1].struct))
+        self._ws, self._ws_bytes = P(self.workspace.data_ptr()), nbytes
+        self._scale_p = P(None if self.scale is None else self.scale.data_ptr())
+        self._closs, self._aloss = P(self.critic_loss.data_ptr()), P(self.actor_loss.data_ptr())
+        self._critic_step, self._actor_step = lib.ctr_td3_critic_step, lib.ctr_ddpg_actor_step
+        self._f32, self._index = torch.float32, device.index
+        self._raw_stream = torch._C._cuda_getCurrentRawStream
+
+    _rows = DdpgLearner._rows
+
+    def critic_step(self, rows, actions, target, stream=None):
+        """One regression step of both critics on ``target`` ([B] float32), as
+        ``DdpgLearner.critic_step`` makes it for one.  The losses go to ``critic_loss`` [2], the
+        gradients to ``critic_grads``."""
+        B = self._rows(rows, self.in_dim, "rows")
+        if self._rows(actions, 6, "actions") != B:
+            raise ValueError("actions has another B than rows")
+        if target.dtype is not self._f32 or target.device != self.device or tuple(target.shape) != (B,) \
+                or not target.is_contiguous():
+            raise ValueError("target must be a contiguous float32 [B] tensor on %s" % (self.device,))
+        s = stream.cuda_stream if stream is not None else self._raw_stream(self._index)
+        rc = self._critic_step(self._critic_pair, self._net_pair, self._critics[0].adam, rows.data_ptr(),
+                               actions.data_ptr(), self._scale_p, target.data_ptr(), B, self._closs, self._ws,
+                               self._ws_bytes, s)
+        if rc:
+            _abi.check(rc, "ctr_td3_critic_step")
+
+    def actor_step(self, rows, stream=None):
+        """One step of the policy up Q1(row, pi(row)) under critic 1's current parameters, which are
+        only read; critic 2 takes no part.  The loss (-mean Q1) goes to ``actor_loss``, the gradients
+        to ``actor_grads``."""
+        B = self._rows(rows, self.in_dim, "rows")
+        s = stream.cuda_stream if stream is not None else self._raw_stream(self._index)
+        a, c = self._actor, self._critics[0]
+        rc = self._actor_step(self._actor_struct, a.struct, a.adam, self._critic_structs[0], c.arrays["W"], c.arrays["b"],
+                              rows.data_ptr(), B, self._aloss, self._ws, self._ws_bytes, s)
+        if rc:
+            _abi.check(rc, "ctr_ddpg_actor_step")
+
+    def state_dict(self):
+        """Adam's state of the three networks, cloned: {"actor": {"m", "v", "pow"}, "critic1": {...},
+        "critic2": {...}}, each as in ``DdpgLearner.state_dict``."""
+        return {"actor": self._actor.state(), "critic1": self._critics[0].state(), "critic2": self._critics[1].state()}
+
+    def load_state_dict(self, state):
+        """Copies a ``state_dict()`` into the learner's own tensors (the device pointers stay)."""
+        self._actor.load_state(state["actor"])
+        self._critics[0].load_state(state["critic1"])
+        self._critics[1].load_state(state["critic2"])

@@ -432,6 +432,61 @@ class ExploreNoise(object):
         return np.where(rnd[:, None], uniform.astype(np.float64), gauss)
 
 
+class TargetSmoothing(object):
+    """TD3's target policy smoothing as ctr_her_sample_td3 applies it (include/ctr_reach_amd.h,
+    "TD3"): Gaussian noise of std ``sigma`` clipped to +-``clip`` on the target action, the sum
+    clipped to the normalised box [-1, 1].  The noise of a row is a pure function of (seed, counter,
+    the row's index in the batch).
+
+        batch = buf.sample_td3(256, actor_targ, critic1_targ, critic2_targ, gamma, sigma=0.2, clip=0.5)
+
+    ``emulate`` is the numpy restatement (no GPU, no library)."""
+
+    STREAM = 7
+
+    def __init__(self, sigma=0.2, clip=0.5):
+        sigma, clip = np.float32(sigma), np.float32(clip)
+        if not (np.isfinite(sigma) and sigma >= 0):
+            raise ValueError("sigma must be finite and >= 0")
+        if not clip >= 0:
+            raise ValueError("clip must be >= 0 (inf: the noise is not clipped)")
+        self.sigma, self.clip = sigma, clip
+
+    def uniforms(self, seed, counter, index):
+        """The six uniforms [n, 6] float32 of rows ``index`` (exact: 24 bits each)."""
+        seed, counter = int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF
+        i = np.asarray(index, dtype=np.uint64).reshape(-1) & np.uint64(0xFFFFFFFF)
+        key = np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint32)
+        w = []
+        for blk in range(2):
+            ctr = np.stack((np.full_like(i, blk), np.full_like(i, counter & 0xFFFFFFFF), i,
+                            np.full_like(i, (counter >> 32) ^ (self.STREAM << 24))), axis=-1).astype(np.uint32)
+            w.append(philox4x32(ctr, key))
+        w = np.concatenate(w, axis=-1)[..., :6]
+        return (w >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+
+    def gaussians(self, seed, counter, index):
+        """The six standard Gaussians [n, 6] float64 of rows ``index``: Box-Muller in plain float64
+        on the exact uniforms."""
+        u64 = self.uniforms(seed, counter, index).astype(np.float64)
+        r = np.sqrt(-2.0 * np.log(1.0 - u64[:, 0:6:2]))
+        ang = float(np.float32(6.2831855)) * u64[:, 1:6:2]
+        return np.stack((r * np.cos(ang), r * np.sin(ang)), axis=-1).reshape(-1, 6)
+
+    def emulate(self, seed, counter, index, actions):
+        """The smoothed actions [n, 6] float64 of the rows ``index`` (their places in the batch) of
+        draw (seed, counter) on the target actions ``actions`` [n, 6] in [-1, 1].  The uniforms are
+        float32 and exact (equal to the device's bits); the Gaussian, the clip and the sum are plain
+        float64 on them.  sigma == 0: the actions' bits."""
+        a32 = np.asarray(actions, dtype=np.float32).reshape(-1, 6)
+        if self.sigma == 0:
+            return a32.astype(np.float64)                      # the no-op case: the bits stay
+        index = np.broadcast_to(np.asarray(index, dtype=np.uint64).reshape(-1), (a32.shape[0],))
+        z = self.gaussians(seed, counter, index)
+        e = np.clip(float(self.sigma) * z, -float(self.clip), float(self.clip))
+        return np.clip(a32.astype(np.float64) + e, -1.0, 1.0)
+
+
 def polyak_(nets, tau, stream=None):
     """The soft (Polyak) update of 1..4 target networks and the refresh of their device blobs in one
     launch (ctr_polyak).  ``nets``: a list of triples ``(net, online, target)``: ``net`` the device

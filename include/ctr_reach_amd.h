@@ -43,6 +43,10 @@
  *   ctr_polyak          the target update of that DDPG (ddpg.py get_target_updates: target <-
  *                       (1 - tau) target + tau online after every training step) together with the
  *                       refresh of the target networks' blobs, one launch for all of them
+ *   ctr_her_sample_td3 / ctr_td3_critic_step
+ *                       no counterpart in the reference, which trains DDPG: the TD3 variant of the two
+ *                       (Fujimoto et al. 2018; stable-baselines' TD3 defaults): the clipped double-Q
+ *                       target on a noise-smoothed target action, and both critics' regression
  *   ctr_explore / ctr_collect
  *                       the data collection of the reference's training pipeline, stable-baselines
  *                       DDPG under HER: NormalActionNoise clipped to the action box and
@@ -739,6 +743,46 @@ typedef struct ctr_her_td_t {
 int ctr_her_sample_td(const ctr_her_t *her, int64_t batch_size, uint64_t seed, uint64_t counter,
                       const ctr_her_batch_t *out, const ctr_her_td_t *td, void *stream);
 
+/* TD3: ctr_her_sample_td with the clipped double-Q target on a smoothed target action (added within
+ * ABI 17: a new symbol, no entry point or struct changes).  It writes everything ctr_her_sample
+ * writes for the same (her, batch_size, seed, counter), bit for bit, and in the same launch, for row
+ * i of the batch,
+ *     a'     = tanhf(y)                                    as ctr_her_sample_td
+ *     e_k    = fminf(fmaxf(sigma * z_k, -clip), clip)      (one f32 product)
+ *     a''_k  = fminf(fmaxf(a'_k + e_k, -1), 1)             (one f32 sum)
+ *     q1, q2 = critic1([next_obs row, a'']), critic2([next_obs row, a''])     (ctr_critic's arithmetic)
+ *     target = done != 0 ? reward : (gamma * fminf(q1, q2)) + reward          (two f32 roundings)
+ * The smoothing noise z_0..z_5 is a pure function of (seed, counter, i), like the row draw (it does
+ * not depend on batch_size, the lane or the workgroup): two Philox4x32-10 blocks blk = 0, 1 of
+ * stream 7, counter {blk, (uint32)counter, (uint32)i, (uint32)(counter >> 32) ^ (7u << 24)}, key
+ * {(uint32)seed, (uint32)(seed >> 32)}; the uniforms u0..u5 from the words w0..w3 | w4, w5 and the
+ * Gaussians z from the uniforms exactly as under "Exploration noise" above (u = (float)(w >> 8) *
+ * 2^-24; r = sqrtf(-2 logf(1 - u_2j)), z_2j = r cosf(t), z_2j+1 = r sinf(t), t = 6.2831855f *
+ * u_2j+1; every product one f32 rounding).  sigma == 0 is a no-op: a'' = a' with its bits, and
+ * nothing is drawn.  clip = INFINITY: the noise is not clipped.
+ * The three blobs take turns in one LDS region beside the sampler's row staging, which is sized for
+ * the largest of them, so every supported actor works with every two supported critics; critic1
+ * and critic2 may be the same struct or blob.  Three launches (the sampler's two scans, then this
+ * kernel); stream-ordered, nothing allocated, nothing read back.
+ * Refused (CTR_EINVAL, before any HIP call, ctr_last_error names ctr_her_sample_td3): whatever
+ * ctr_her_sample_td refuses, of actor, critic1 and critic2; a NULL td or td->target; a non-finite
+ * gamma; a sigma that is not finite or negative; a clip that is NaN or negative.  batch_size = 0 is
+ * a no-op. */
+typedef struct ctr_her_td3_t {
+    const ctr_actor_t  *actor;     /* target policy; its scale is not read                  */
+    const ctr_critic_t *critic1;   /* target critics; they may be the same struct / blob    */
+    const ctr_critic_t *critic2;
+    float   gamma;                 /* finite                                                */
+    float   sigma;                 /* finite, >= 0: std of the smoothing noise, in the normalised box */
+    float   clip;                  /* >= 0, not NaN; INFINITY = the noise is not clipped    */
+    int32_t pad;
+    float  *target;                /* [B] device, required                                  */
+    float  *q1_next, *q2_next;     /* [B] or NULL                                           */
+    float  *next_action;           /* [B][6] or NULL: the SMOOTHED target action a''        */
+} ctr_her_td3_t;
+int ctr_her_sample_td3(const ctr_her_t *her, int64_t batch_size, uint64_t seed, uint64_t counter,
+                       const ctr_her_batch_t *out, const ctr_her_td3_t *td, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * The soft (Polyak) update of target networks and the refresh of their blobs, in one launch for up
  * to CTR_POLYAK_MAX_NETS networks (added within ABI 17: a new symbol, no entry point or struct
@@ -840,6 +884,29 @@ int ctr_ddpg_critic_step(const ctr_critic_t *critic, const ctr_ddpg_net_t *net, 
 int ctr_ddpg_actor_step(const ctr_actor_t *actor, const ctr_ddpg_net_t *net, const ctr_ddpg_adam_t *adam,
                         const ctr_critic_t *critic, const float *const *critic_W, const float *const *critic_b,
                         const float *rows, int64_t B, float *loss, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* TD3's twin critics: ctr_ddpg_critic_step on critic[0] / net[0] and on critic[1] / net[1], on the
+ * same rows, actions, scale and target and with the same Adam constants, in the two launches of one
+ * such call (added within ABI 17: new symbols).  The grids get a second dimension and plane y works
+ * on critic y, with ctr_ddpg_critic_step's arithmetic, tile-to-slot dealing and summation order:
+ * every tensor of both nets (parameters, gradients, m, v, pow) and loss[0], loss[1] (device
+ * float[2], or NULL) are what the two ctr_ddpg_critic_step calls leave, bit for bit.  The critics
+ * may have different hidden shapes (one in_dim).
+ * workspace: critic[0]'s region, laid out as ctr_ddpg_critic_step lays it out for this B, then
+ * critic[1]'s behind it (a region is a multiple of 16 B).  ctr_td3_workspace_bytes(actor, critic1,
+ * critic2, max_B) is the larger of the two regions' sum at max_B and what ctr_ddpg_actor_step
+ * needs, so one workspace serves a whole TD3 learner (-1 on a refused shape or max_B outside
+ * 1..65 536).
+ * Refused (CTR_EINVAL, before any HIP call, ctr_last_error names the function): whatever
+ * ctr_ddpg_critic_step refuses for either net; a NULL array or array entry; critics of different
+ * in_dim; the two nets sharing any W, b, gradient, state or pow tensor (the planes would race). */
+int64_t ctr_td3_workspace_bytes(const ctr_actor_t *actor, const ctr_critic_t *critic1,
+                                const ctr_critic_t *critic2, int64_t max_B);
+int ctr_td3_critic_step(const ctr_critic_t *const critic[2], const ctr_ddpg_net_t *const net[2],
+                        const ctr_ddpg_adam_t *adam, const float *rows, const float *actions,
+                        const float *scale, const float *target, int64_t B,
+                        float *loss /* device float[2] or NULL */,
+                        void *workspace, int64_t workspace_bytes, void *stream);
 
 /* CtrReachEnv.reset for the environments with mask[i] != 0 (mask NULL = all).
  * goal [n][3] or NULL (sample a goal), system [n] or NULL (sample uniformly).
