@@ -54,9 +54,23 @@ under critic 1 and one ``polyak_`` of the three target networks.  ``TARGET_NOISE
 0.5 and ``POLICY_DELAY`` 2 are TD3's published defaults and stable-baselines'.  The critic loss
 reported is the mean of the two critics'.
 
+With ``--sac`` (``main(..., sac=True)``; an error together with ``--td3``, and it implies nothing of the
+DDPG path) the loop trains SAC (Haarnoja et al. 2018, with the learned temperature) instead: a policy
+with a 12-row head (six means, six log standard deviations, no Tanh) as a ``GaussianActor`` ``pi_dev``,
+two critics with their targets (``MlpCritic`` blobs) and no target policy.  Collection is per step
+``venv.step(pi_dev.sample(venv.actor_rows(), counter=step, row_base=venv.env_base)["action"])`` with the
+fused HER feed, two launches a step: the policy's own noise explores.  An update is ``her.sample``, the
+next action and its log-probability from ``pi_dev.sample(next_obs, counter)``, the two target critics on
+it, ``target = r + gamma (1 - done) (min(Q1', Q2') - alpha logp')`` in torch on the device,
+``SacLearner.critic_step`` (``Td3Learner``'s), ``SacLearner.actor_step`` (the policy's step under both
+critics and the temperature's), ``pi_dev.load_(policy)`` and one ``polyak_`` of the two target critics.
+``SAC_LR`` 3e-4, ``SAC_TAU`` 0.005, ``init_alpha`` 1 and ``target_entropy`` -6 are stable-baselines SAC's
+defaults with ``ent_coef='auto'``.  ``pi_dev.mean_actor()`` gives the trained policy's deterministic mean
+to ``venv.rollout`` / ``follow`` for evaluation.
+
 usage: python examples/train_ddpg_her.py [--num-envs N] [--iterations I] [--steps-per-iter S]
            [--batch-size B] [--updates-per-iter U] [--hidden 64,64] [--seed 0] [--device cuda]
-           [--device-targets] [--device-polyak] [--device-update] [--td3]"""
+           [--device-targets] [--device-polyak] [--device-update] [--td3] [--sac]"""
 import argparse
 import os
 import sys
@@ -68,13 +82,14 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-ctr-reach_amd"))
 from ctr_reach_amd import CtrReachVecEnv  # noqa: E402
-from ctr_reach_amd.learner import DdpgLearner, Td3Learner  # noqa: E402
-from ctr_reach_amd.policy import ExploreNoise, MlpActor, MlpCritic, polyak_  # noqa: E402
+from ctr_reach_amd.learner import DdpgLearner, SacLearner, Td3Learner  # noqa: E402
+from ctr_reach_amd.policy import ExploreNoise, GaussianActor, MlpActor, MlpCritic, polyak_  # noqa: E402
 
 GAMMA, TAU, ACTOR_LR, CRITIC_LR = 0.99, 0.001, 1e-4, 1e-3
 N_SAMPLED_GOAL, STRATEGY = 4, "future"
 SIGMA, RANDOM_EPS = 0.2, 0.3
 TARGET_NOISE, NOISE_CLIP, POLICY_DELAY = 0.2, 0.5, 2                         # TD3 (--td3)
+SAC_LR, SAC_TAU, INIT_ALPHA, TARGET_ENTROPY = 3e-4, 0.005, 1.0, -6.0          # SAC (--sac)
 
 
 def mlp(n_in, hidden, n_out, tanh):
@@ -89,7 +104,11 @@ def mlp(n_in, hidden, n_out, tanh):
 
 
 def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, updates_per_iter=40, hidden=(64, 64), seed=0,
-         device="cuda", device_targets=False, device_polyak=False, device_update=False, td3=False):
+         device="cuda", device_targets=False, device_polyak=False, device_update=False, td3=False, sac=False):
+    if sac and td3:
+        raise ValueError("--sac and --td3 are two algorithms: choose one")
+    if sac:
+        return main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter, hidden, seed, device)
     device = torch.device(device)
     device_update = device_update or td3
     device_polyak = device_polyak or device_update
@@ -206,6 +225,55 @@ def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, update
                 rollout_stats=venv.rollout_stats, venv=venv, her=her)
 
 
+def main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter, hidden, seed, device):
+    """``main(..., sac=True)``: the same loop with SAC's pieces (the module docstring)."""
+    device = torch.device(device)
+    torch.manual_seed(seed)
+    venv = CtrReachVecEnv(num_envs, device=device, seed=seed)
+    her = venv.enable_her(n_sampled_goal=N_SAMPLED_GOAL, goal_selection_strategy=STRATEGY)
+    venv.reset()
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    venv.t.copy_(torch.randint(0, venv.max_steps_per_episode, (num_envs,), generator=g, dtype=torch.int32))
+
+    d = venv.obs_dim + 6
+    policy = mlp(d, hidden, 12, False).to(device).requires_grad_(False)       # six means, six log standard deviations
+    critics = [mlp(d + 6, hidden, 1, False).to(device).requires_grad_(False) for _ in range(2)]
+    targets = [mlp(d + 6, hidden, 1, False).to(device).requires_grad_(False) for _ in range(2)]
+    for critic, targ in zip(critics, targets):
+        targ.load_state_dict(critic.state_dict())
+    learner = SacLearner(policy, critics[0], critics[1], scale=venv.action_space.high, actor_lr=SAC_LR, critic_lr=SAC_LR,
+                         alpha_lr=SAC_LR, init_alpha=INIT_ALPHA, target_entropy=TARGET_ENTROPY, max_batch=batch_size, seed=seed)
+    pi_dev = GaussianActor.from_torch(policy, venv.action_space.high, device, seed=seed)
+    targets_dev = [MlpCritic.from_torch(targ, device) for targ in targets]
+    losses = []
+    step = update = 0
+    for it in range(iterations):
+        for _ in range(steps_per_iter):                                      # the policy's sample, the step with its HER feed
+            venv.step(pi_dev.sample(venv.actor_rows(), counter=step, row_base=venv.env_base)["action"])
+            step += 1
+        critic_sum = torch.zeros((), device=device)
+        policy_sum = torch.zeros((), device=device)
+        for _ in range(updates_per_iter):
+            batch = her.sample(batch_size)
+            # the sampling draws and the collection draws share the key: keep their counters apart
+            nxt = pi_dev.sample(batch["next_obs"], counter=(1 << 40) + update)
+            update += 1
+            q = torch.minimum(targets_dev[0](batch["next_obs"], nxt["unit"]), targets_dev[1](batch["next_obs"], nxt["unit"]))
+            target = batch["reward"] + GAMMA * (1.0 - batch["done"]) * (q - learner.alpha * nxt["logp"])
+            learner.critic_step(batch["obs"], batch["action"], target)
+            learner.actor_step(batch["obs"])
+            pi_dev.load_(policy)
+            polyak_([(targets_dev[0], critics[0], targets[0]), (targets_dev[1], critics[1], targets[1])], SAC_TAU)
+            critic_sum += learner.critic_loss.mean()
+            policy_sum += learner.actor_loss
+        # the iteration's only host read
+        losses.append((critic_sum.item() / max(updates_per_iter, 1), policy_sum.item() / max(updates_per_iter, 1)))
+    return dict(policy=policy, pi_dev=pi_dev, critic=critics[0], critic2=critics[1], critic_targ=targets[0],
+                critic2_targ=targets[1], critic_targ_dev=targets_dev[0], critic2_targ_dev=targets_dev[1], learner=learner,
+                losses=losses, alpha=learner.alpha, venv=venv, her=her)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--num-envs", type=int, default=4096)
@@ -223,12 +291,17 @@ if __name__ == "__main__":
                     help="the critic's and the policy's updates from a DdpgLearner, no autograd (implies --device-polyak)")
     ap.add_argument("--td3", action="store_true",
                     help="TD3: twin critics, smoothed clipped double-Q targets, delayed policy updates (implies --device-update)")
+    ap.add_argument("--sac", action="store_true",
+                    help="SAC: a tanh-Gaussian policy, twin critics, the learned temperature (not with --td3)")
     args = ap.parse_args()
     out = main(args.num_envs, args.iterations, args.steps_per_iter, args.batch_size, args.updates_per_iter,
                tuple(int(w) for w in args.hidden.split(",")), args.seed, args.device, args.device_targets,
-               args.device_polyak, args.device_update, args.td3)
+               args.device_polyak, args.device_update, args.td3, args.sac)
     for it, (c, p) in enumerate(out["losses"]):
         print("iteration %3d: critic loss %.4g, policy loss %.4g" % (it, c, p))
-    stats = out["rollout_stats"]
-    episodes, successes = int(stats["episodes"].sum()), int(stats["successes"].sum())
-    print("%d episodes finished, %d reached their goal; %d rows in the HER store" % (episodes, successes, len(out["her"])))
+    if args.sac:
+        print("alpha %.4g; %d rows in the HER store" % (float(out["alpha"]), len(out["her"])))
+    else:
+        stats = out["rollout_stats"]
+        episodes, successes = int(stats["episodes"].sum()), int(stats["successes"].sum())
+        print("%d episodes finished, %d reached their goal; %d rows in the HER store" % (episodes, successes, len(out["her"])))

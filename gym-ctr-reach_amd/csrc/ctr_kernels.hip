@@ -33,6 +33,11 @@
 //                 (ctr_her_sample_td3; ctr_critic.inc)
 //   k_td3_grad, k_td3_apply  k_ddpg_grad<false> and k_ddpg_apply on TD3's two critics at once, plane
 //                 blockIdx.y of the grid on critic y (ctr_td3_critic_step; ctr_ddpg.inc)
+//   k_gauss_act   k_actor with a 12-row head: SAC's tanh-Gaussian policy, an action and its
+//                 log-probability per row (ctr_gauss_act; ctr_sac.inc)
+//   k_sac_grad, k_sac_apply  SAC's policy loss under the smaller of two critics, k_ddpg_grad<true> with
+//                 three networks' tiles in LDS, and k_ddpg_apply with the temperature's step in one
+//                 thread (ctr_sac_actor_step; ctr_sac.inc)
 //   k_collect     k_rollout with exploration noise on each action and each step recorded into the HER
 //                 store (ctr_collect, at the end of the file)
 //   k_explore     the exploration noise alone, one env per lane (ctr_explore; explore_lane, ctr_device.hpp)
@@ -3208,3 +3213,4 @@ int ctr_follow(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_
 #include "ctr_critic.inc"
 #include "ctr_polyak.inc"
 #include "ctr_ddpg.inc"
+#include "ctr_sac.inc"

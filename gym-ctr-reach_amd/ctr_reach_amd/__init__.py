@@ -11,6 +11,8 @@ with the environments stepped in lockstep by hand-written HIP kernels on gfx950.
   MlpActor         the policy's actor, run by hand-written kernels (rollout, collect, follow)
   DdpgLearner      DDPG's critic and actor updates (forward, backward, Adam) on the device
   Td3Learner       the same with TD3's twin critics, both regressed in one pair of launches
+  GaussianActor    SAC's tanh-Gaussian policy: an action and its log-probability in one launch
+  SacLearner       SAC's policy step under twin critics with the learned temperature, on the device
   paths            line / circle / helix waypoint paths for follow() and dls_ik_path
 """
 from .vec_env import CtrReachVecEnv, FollowResult  # noqa: F401
@@ -19,7 +21,7 @@ from .systems import Tube, default_kwargs, default_systems_parameters  # noqa: F
 from .goal_tolerance import GoalTolerance  # noqa: F401
 from .ik import dls_ik_path, dls_ik_position_only  # noqa: F401
 from .her import HerReplayBuffer  # noqa: F401
-from .policy import MlpActor, MlpCritic, TargetSmoothing, polyak_  # noqa: F401
-from .learner import DdpgLearner, Td3Learner  # noqa: F401
+from .policy import GaussianActor, MlpActor, MlpCritic, TargetSmoothing, polyak_  # noqa: F401
+from .learner import DdpgLearner, SacLearner, Td3Learner  # noqa: F401
 from .paths import circle_path, helix_path, line_path  # noqa: F401
 from . import paths  # noqa: F401

@@ -1,0 +1,33 @@
+"""ctypes mirror of ctr_sac_alpha_t and the prototypes of ctr_gauss_blob_bytes, ctr_gauss_pack,
+ctr_gauss_load, ctr_gauss_act, ctr_sac_workspace_bytes and ctr_sac_actor_step
+(include/ctr_reach_amd.h, "SAC": added within ABI 17).  ``_abi.load`` binds them;
+tests/test_host_sac.py checks the mirror against the header."""
+import ctypes
+
+from ._abi import CtrActor, _P
+from ._abi_critic import CtrCritic
+from ._abi_ddpg import CtrDdpgAdam, CtrDdpgNet
+from ._abi_td3 import CriticPair
+
+
+class CtrSacAlpha(ctypes.Structure):
+    """ctr_sac_alpha_t: the temperature's Adam state, gradient, learning rate and switch."""
+    _fields_ = [("state", _P), ("grad", _P), ("lr", ctypes.c_float), ("learn", ctypes.c_int32)]
+
+
+LayersPair = ctypes.POINTER(_P) * 2                # const float *const *const critic_W[2]
+
+
+def bind(L):
+    i64, u64, i32 = ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32
+    A = ctypes.POINTER(CtrActor)
+    L.ctr_gauss_blob_bytes.argtypes = [A]
+    L.ctr_gauss_blob_bytes.restype = i64
+    L.ctr_gauss_pack.argtypes = [A, ctypes.POINTER(_P), ctypes.POINTER(_P), _P]
+    L.ctr_gauss_load.argtypes = [A, ctypes.POINTER(_P), ctypes.POINTER(_P), _P]
+    L.ctr_gauss_act.argtypes = [A, _P, i64, u64, u64, i64, i32, _P, _P, _P, _P, _P]
+    L.ctr_sac_workspace_bytes.argtypes = [A, ctypes.POINTER(CtrCritic), ctypes.POINTER(CtrCritic), i64]
+    L.ctr_sac_workspace_bytes.restype = i64
+    L.ctr_sac_actor_step.argtypes = [A, ctypes.POINTER(CtrDdpgNet), ctypes.POINTER(CtrDdpgAdam), ctypes.POINTER(CriticPair),
+                                     ctypes.POINTER(LayersPair), ctypes.POINTER(LayersPair), _P, i64, u64, u64, _P,
+                                     ctypes.POINTER(CtrSacAlpha), ctypes.c_float, _P, _P, _P, i64, _P]

@@ -10,8 +10,9 @@ parameters.  No autograd and no torch optimiser:
     polyak_([(actor_targ, policy, policy_targ), (critic_targ_dev, critic, critic_targ)], 0.001)
 
 ``Td3Learner`` is the same learner with TD3's two critics, both regressed by one call
-(ctr_td3_critic_step).  ``adam_reference`` is the numpy float32 restatement of the Adam step (the
-kernel gives its bits).
+(ctr_td3_critic_step).  ``SacLearner`` is SAC: the same twin critic step, and the stochastic policy's
+step under both critics with the learned temperature (ctr_sac_actor_step).  ``adam_reference`` is the
+numpy float32 restatement of the Adam step (the kernel gives its bits).
 """
 import ctypes
 
@@ -287,9 +288,18 @@ class Td3Learner(object):
 
     def __init__(self, policy, critic1, critic2, scale=None, actor_lr=1e-4, critic_lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  max_batch=256, alloc=None):
+        self._setup(policy, True, 6, critic1, critic2, scale, (("actor_lr", actor_lr), ("critic_lr", critic_lr)), betas, eps,
+                    max_batch, alloc, "ctr_td3_workspace_bytes")
+        self._actor_step = self._lib.ctr_ddpg_actor_step
+
+    def _setup(self, policy, tanh, out_rows, critic1, critic2, scale, rates, betas, eps, max_batch, alloc, workspace_fn):
+        """The constructor's work, which ``SacLearner`` shares: the checks, the three ``_Net``, the
+        workspace (``workspace_fn``'s bytes) and everything ``critic_step`` takes.  ``tanh``,
+        ``out_rows``: the policy's head; ``rates``: ((name, value), ...), every value finite, the
+        first two the policy's and the critics' learning rates."""
         import torch
         from . import _abi_ddpg, _abi_td3
-        a_params, a_in, a_hidden = _masters(policy, True, "policy", (19, 20), 6,
+        a_params, a_in, a_hidden = _masters(policy, tanh, "policy", (19, 20), out_rows,
                                             "the policy's rows are obs_dim + 6 = 19 or 20 floats")
         c_nets = []
         for critic, name in ((critic1, "critic1"), (critic2, "critic2")):
@@ -306,7 +316,7 @@ class Td3Learner(object):
                for p1 in c_nets[0][0] for t1 in p1 for p2 in c_nets[1][0] for t2 in p2):
             raise ValueError("critic1 and critic2 share a tensor: the twin step updates them side by side")
         betas = (float(betas[0]), float(betas[1]))
-        for name, val in (("actor_lr", actor_lr), ("critic_lr", critic_lr), ("eps", eps)):
+        for name, val in tuple(rates) + (("eps", eps),):
             if not np.isfinite(float(val)):
                 raise ValueError(name + " must be finite")
         if not all(0.0 <= b < 1.0 for b in betas):
@@ -334,13 +344,14 @@ class Td3Learner(object):
             s.in_dim, s.n_hidden = in_dim, len(hidden)
             for l, w in enumerate(hidden):
                 s.width[l] = w
+        actor_lr, critic_lr = rates[0][1], rates[1][1]
         self._actor = _Net(a_params, alloc, actor_lr, betas, eps)
         self._critics = (_Net(c_nets[0][0], alloc, critic_lr, betas, eps), _Net(c_nets[1][0], alloc, critic_lr, betas, eps))
         self.actor_grads = self._actor.grads
         self.critic_grads = (self._critics[0].grads, self._critics[1].grads)
-        nbytes = int(lib.ctr_td3_workspace_bytes(sa, sc[0], sc[1], max_batch))
+        nbytes = int(getattr(lib, workspace_fn)(sa, sc[0], sc[1], max_batch))
         if nbytes < 0:
-            raise _abi.CtrError("ctr_td3_workspace_bytes: " + lib.ctr_last_error().decode())
+            raise _abi.CtrError(workspace_fn + ": " + lib.ctr_last_error().decode())
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
         if self.workspace.data_ptr() % 16:
             raise RuntimeError("workspace not 16-B aligned")
@@ -354,7 +365,7 @@ class Td3Learner(object):
         self._ws, self._ws_bytes = P(self.workspace.data_ptr()), nbytes
         self._scale_p = P(None if self.scale is None else self.scale.data_ptr())
         self._closs, self._aloss = P(self.critic_loss.data_ptr()), P(self.actor_loss.data_ptr())
-        self._critic_step, self._actor_step = lib.ctr_td3_critic_step, lib.ctr_ddpg_actor_step
+        self._critic_step = lib.ctr_td3_critic_step
         self._f32, self._index = torch.float32, device.index
         self._raw_stream = torch._C._cuda_getCurrentRawStream
 
@@ -399,3 +410,99 @@ class Td3Learner(object):
         self._actor.load_state(state["actor"])
         self._critics[0].load_state(state["critic1"])
         self._critics[1].load_state(state["critic2"])
+
+
+class SacLearner(object):
+    """SAC (Haarnoja et al. 2018, with the learned temperature) on the device: ``policy`` an
+    ``nn.Sequential(Linear, ReLU, ..., Linear(h, 12))`` as ``GaussianActor.from_torch`` takes it (six
+    means, six log standard deviations, no Tanh), ``critic1`` and ``critic2`` as ``Td3Learner`` takes
+    them; all given as ``DdpgLearner`` takes its networks.
+
+        learner = SacLearner(policy, critic1, critic2, scale=venv.action_space.high)
+        batch = her.sample(256)
+        nxt = pi.sample(batch["next_obs"], counter)
+        q = torch.minimum(critic1_targ_dev(batch["next_obs"], nxt["unit"]), critic2_targ_dev(batch["next_obs"], nxt["unit"]))
+        target = batch["reward"] + gamma * (1 - batch["done"]) * (q - learner.alpha * nxt["logp"])
+        learner.critic_step(batch["obs"], batch["action"], target)
+        learner.actor_step(batch["obs"])
+        pi.load_(policy)
+        polyak_([(critic1_targ_dev, critic1, critic1_targ), (critic2_targ_dev, critic2, critic2_targ)], 0.005)
+
+    ``critic_step`` is ``Td3Learner.critic_step`` (the same C call).  ``actor_step`` (ctr_sac_actor_step,
+    two launches) samples an action per row from the policy with the noise of (``seed``, ``counter``,
+    the row's index), and descends mean(alpha * logp - min(Q1, Q2)) through both critics, the tanh and
+    the reparametrisation; with ``learn_alpha`` the temperature's ``log_alpha`` then takes its own Adam
+    step on -log_alpha * (logp_mean + target_entropy).  The learning rates, ``init_alpha`` and
+    ``target_entropy`` = -dim(A) are stable-baselines SAC's defaults with ``ent_coef='auto'``.
+    ``actor_loss``, ``logp_mean``, ``log_alpha``, ``alpha_grad`` (0-d) and ``alpha_state`` ([4]: m, v,
+    beta1^t, beta2^t) stay on the device; ``alpha`` is exp(log_alpha) as a device tensor."""
+
+    def __init__(self, policy, critic1, critic2, scale=None, actor_lr=3e-4, critic_lr=3e-4, alpha_lr=3e-4, init_alpha=1.0,
+                 target_entropy=-6.0, learn_alpha=True, betas=(0.9, 0.999), eps=1e-8, max_batch=256, alloc=None, seed=0):
+        import torch
+        from . import _abi_sac
+        if not (np.isfinite(float(init_alpha)) and float(init_alpha) > 0.0):
+            raise ValueError("init_alpha must be positive and finite")
+        self._setup(policy, False, 12, critic1, critic2, scale,
+                    (("actor_lr", actor_lr), ("critic_lr", critic_lr), ("alpha_lr", alpha_lr), ("target_entropy", target_entropy)),
+                    betas, eps, max_batch, alloc, "ctr_sac_workspace_bytes")
+        device = self.device
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.counter = 0
+        self.target_entropy, self.learn_alpha = float(target_entropy), bool(learn_alpha)
+        self.logp_mean = torch.zeros((), dtype=torch.float32, device=device)
+        self.log_alpha = torch.tensor(float(np.log(np.float64(init_alpha))), dtype=torch.float32, device=device)
+        self.alpha_state = torch.tensor([0.0, 0.0, 1.0, 1.0], dtype=torch.float32, device=device)
+        self.alpha_grad = torch.zeros((), dtype=torch.float32, device=device)
+        # what ctr_sac_actor_step takes beyond the twin step's arguments, once
+        P = ctypes.c_void_p
+        self._cW = _abi_sac.LayersPair(self._critics[0].arrays["W"], self._critics[1].arrays["W"])
+        self._cb = _abi_sac.LayersPair(self._critics[0].arrays["b"], self._critics[1].arrays["b"])
+        self._alpha_struct = _abi_sac.CtrSacAlpha(self.alpha_state.data_ptr(), self.alpha_grad.data_ptr(), float(alpha_lr),
+                                                  int(self.learn_alpha))
+        self._lpm, self._la = P(self.logp_mean.data_ptr()), P(self.log_alpha.data_ptr())
+        self._actor_step = self._lib.ctr_sac_actor_step
+
+    _rows = DdpgLearner._rows
+    _setup = Td3Learner._setup
+    critic_step = Td3Learner.critic_step
+
+    @property
+    def alpha(self):
+        """exp(log_alpha): a 0-d device tensor (no host read)."""
+        return self.log_alpha.exp()
+
+    def actor_step(self, rows, counter=None, stream=None):
+        """One step of the policy down mean(alpha * logp - min(Q1, Q2)) on actions sampled with the
+        noise of (seed, ``counter``, row), under both critics' current parameters, which are only
+        read; then the temperature's step (``learn_alpha``).  ``counter`` None: a count the learner
+        keeps, advanced by every such call.  The loss goes to ``actor_loss``, the mean log-probability
+        to ``logp_mean``, the gradients to ``actor_grads`` and ``alpha_grad``."""
+        B = self._rows(rows, self.in_dim, "rows")
+        if counter is None:
+            counter = self.counter
+            self.counter += 1
+        s = stream.cuda_stream if stream is not None else self._raw_stream(self._index)
+        a = self._actor
+        rc = self._actor_step(self._actor_struct, a.struct, a.adam, self._critic_pair, self._cW, self._cb, rows.data_ptr(), B,
+                              self.seed, int(counter) & 0xFFFFFFFFFFFFFFFF, self._la, self._alpha_struct, self.target_entropy,
+                              self._aloss, self._lpm, self._ws, self._ws_bytes, s)
+        if rc:
+            _abi.check(rc, "ctr_sac_actor_step")
+
+    def state_dict(self):
+        """Adam's state of the three networks as ``Td3Learner.state_dict`` gives it, with the
+        temperature (``log_alpha``, ``alpha_state``: cloned) and the noise ``counter``."""
+        return {"actor": self._actor.state(), "critic1": self._critics[0].state(), "critic2": self._critics[1].state(),
+                "log_alpha": self.log_alpha.clone(), "alpha_state": self.alpha_state.clone(), "counter": self.counter}
+
+    def load_state_dict(self, state):
+        """Copies a ``state_dict()`` into the learner's own tensors (the device pointers stay)."""
+        if tuple(state["alpha_state"].shape) != (4,) or tuple(state["log_alpha"].shape) != ():
+            raise ValueError("state: log_alpha is 0-d and alpha_state has 4 elements")
+        self._actor.load_state(state["actor"])
+        self._critics[0].load_state(state["critic1"])
+        self._critics[1].load_state(state["critic2"])
+        self.log_alpha.copy_(state["log_alpha"])
+        self.alpha_state.copy_(state["alpha_state"])
+        self.counter = int(state["counter"])

@@ -14,6 +14,9 @@ target policy and a target critic on every sampled row and returns the DDPG targ
 ``polyak_`` is the soft update of such target networks' float32 parameters together with the
 refresh of their blobs, one launch for all of them (ctr_polyak).
 
+``GaussianActor`` is SAC's tanh-Gaussian policy on the actor's kernels (ctr_gauss_act): a 12-row head,
+an action sampled with its log-probability in one launch, and its deterministic mean as an ``MlpActor``.
+
 ``ExploreNoise`` is the exploration noise of the reference's DDPG + HER training on such an actor's
 actions (ctr_explore / ctr_collect), with its own numpy restatement.
 """
@@ -487,6 +490,147 @@ class TargetSmoothing(object):
         return np.clip(a32.astype(np.float64) + e, -1.0, 1.0)
 
 
+def gauss_head(y, eps, scale, dtype=np.float64):
+    """The tanh-Gaussian head (include/ctr_reach_amd.h, "SAC") on the head's outputs ``y`` [n, 12] and
+    the standard normals ``eps`` [n, 6], every operation in ``dtype`` and in the header's order:
+    dict(action, unit, logp, s, u).  float64 is the reference; float32 restates the kernel's roundings
+    (numpy's exp, tanh and log1p in place of the device's)."""
+    f = np.dtype(dtype).type
+    y, eps, scale = np.asarray(y, dtype=f), np.asarray(eps, dtype=f), np.asarray(scale, dtype=f).reshape(6)
+    with np.errstate(over="ignore", under="ignore"):
+        s = np.minimum(np.maximum(y[:, 6:], f(-20)), f(2))
+        u = (np.exp(s) * eps + y[:, :6]) if dtype == np.float64 else \
+            (np.exp(s).astype(np.float64) * eps.astype(np.float64) + y[:, :6].astype(np.float64)).astype(f)   # fmaf
+        t = np.tanh(u)
+        x = f(-2) * u
+        softplus = np.maximum(x, f(0)) + np.log1p(np.exp(-np.abs(x)))
+        a = (f(-0.5) * (eps * eps) - s) - f(0.9189385332046727)
+        c = f(2) * ((f(0.6931471805599453) - u) - softplus)
+        term = a - c
+        logp = np.zeros(len(y), dtype=f)
+        for i in range(6):
+            logp = logp + term[:, i]
+    return dict(action=scale * t, unit=t, logp=logp, s=s, u=u)
+
+
+class GaussianActor(_Mlp):
+    """SAC's tanh-Gaussian policy on the device (ctr_gauss_act, include/ctr_reach_amd.h "SAC"):
+    ``MlpActor``'s network with a 12-row output layer and no Tanh behind it, rows 0..5 the mean and
+    rows 6..11 the log standard deviation (clipped to [-20, 2]).  ``layers`` / ``from_torch`` as
+    ``MlpActor`` takes them (``nn.Sequential(Linear, ReLU, ..., Linear(h, 12))``), ``scale`` the
+    action space's high, ``seed`` the key of the noise.
+
+        pi = GaussianActor.from_torch(policy, venv.action_space.high, "cuda")
+        out = pi.sample(venv.actor_rows(), counter=step, row_base=venv.env_base)
+        venv.step(out["action"])                  # out["unit"] is what a critic takes, out["logp"] its log-probability
+        pi.load_(policy)                          # after the learner's step: ctr_gauss_load
+        venv.rollout(pi.mean_actor(), 20)         # the deterministic mean through the period kernels
+
+    The noise of a row is a pure function of (seed, counter, row_base + the row's index).
+    ``emulate`` is the numpy restatement (no GPU, no library)."""
+
+    NAME, IN_DIMS, OUT, TANH = "actor", (19, 20), 12, False
+    STREAM = 8
+    _IN_MSG = "the first layer takes the flat row of obs_dim + 6 = 19 or 20 floats"
+    _OUT_MSG = "the output layer has 12 rows (six means, six log standard deviations)"
+
+    def __init__(self, layers, scale, device=None, seed=0):
+        self._init_layers(layers, _abi.CtrActor())
+        self.scale = np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
+        if self.scale.shape != (6,) or not np.isfinite(self.scale).all():
+            raise ValueError("scale must be 6 finite floats")
+        for i in range(6):
+            self._struct.scale[i] = float(self.scale[i])
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._mean = self._mean_sources = None
+        if device is not None:
+            self._upload(device)
+
+    @classmethod
+    def from_torch(cls, seq, scale, device=None, seed=0):
+        """From an ``nn.Sequential`` of Linear, ReLU, ..., Linear(h, 12)."""
+        return cls(_sequential_layers(seq, False, "policy"), scale, device, seed)
+
+    def _fn(self, what):
+        return "ctr_gauss_" + what
+
+    def uniforms(self, counter, index):
+        """The six uniforms [n, 6] float32 of rows ``index`` (row_base + the row) of draw ``counter``
+        (exact: 24 bits each)."""
+        return TargetSmoothing.uniforms(self, self.seed, counter, index)
+
+    def gaussians(self, counter, index, dtype=np.float64):
+        """The six standard normals [n, 6] of rows ``index``: Box-Muller in ``dtype`` on the exact
+        uniforms (float64: the reference; float32: numpy's restatement of the kernel's roundings)."""
+        f = np.dtype(dtype).type
+        u = self.uniforms(counter, index).astype(f)
+        r = np.sqrt(f(-2) * np.log(f(1) - u[:, 0:6:2]))
+        ang = f(np.float32(6.2831855)) * u[:, 1:6:2]
+        return np.stack((r * np.cos(ang), r * np.sin(ang)), axis=-1).reshape(-1, 6)
+
+    def emulate(self, rows, counter, row_base=0, deterministic=False):
+        """The policy's arithmetic in numpy: the bf16 head as the kernel makes it, then the header's
+        formulas in float64 on the exact uniforms: dict(action, unit, logp [n], logits [n, 12], s, u)."""
+        self._need_host()
+        x = np.asarray(rows, dtype=np.float32).reshape(-1, self.in_dim)
+        with np.errstate(invalid="ignore", over="ignore"):
+            y = self._emulate_output(x)
+        n = len(x)
+        eps = np.zeros((n, 6)) if deterministic else self.gaussians(counter, int(row_base) + np.arange(n))
+        out = gauss_head(y, eps, self.scale)
+        out["logits"] = y
+        return out
+
+    def mean_layers(self, layers):
+        """``layers`` as ``load_`` takes them with the output layer cut to its first six rows (the
+        mean; contiguous views, nothing copied): what the mean actor's ``load_`` takes."""
+        import torch
+        if isinstance(layers, torch.nn.Module):
+            layers = _sequential_layers(layers, False, "policy", detach=False)
+        layers = [tuple(pair) for pair in layers]
+        W, b = layers[-1]
+        return layers[:-1] + [(W[:6], b[:6])]
+
+    def mean_actor(self):
+        """The policy's deterministic mean as an ``MlpActor`` on the same device (action = scale *
+        tanh(mu)), for ``venv.rollout`` / ``follow`` / ``collect`` and the path comparisons.  Built
+        once; after a ``load_`` the next call refreshes it from the same device parameters."""
+        if self.blob is None:
+            raise RuntimeError("the policy is on the host (GaussianActor(..., device=None))")
+        if self._mean is None:
+            if self.weights is not None:
+                layers = list(zip(self.weights[:-1], self.biases[:-1])) + [(self.weights[-1][:6], self.biases[-1][:6])]
+            else:
+                layers = self.mean_layers(self._sources)
+            self._mean = MlpActor(layers, self.scale, self.device)
+            self._mean_sources = self._sources
+        elif self._sources is not None and self._mean_sources is not self._sources:
+            self._mean.load_(self.mean_layers(self._sources))
+            self._mean_sources = self._sources
+        return self._mean
+
+    def sample(self, rows, counter, row_base=0, deterministic=False, logits=False, stream=None):
+        """ctr_gauss_act: rows [n, in_dim] float32 device tensor -> dict(action [n, 6], unit [n, 6],
+        logp [n]) and with ``logits`` the head's outputs [n, 12].  One launch."""
+        import torch
+        if self.blob is None:
+            raise RuntimeError("the policy is on the host (GaussianActor(..., device=None))")
+        rows = rows.to(device=self.device, dtype=torch.float32).contiguous()
+        if rows.dim() != 2 or rows.shape[1] != self.in_dim:
+            raise ValueError("rows must be [n, %d]" % self.in_dim)
+        n = rows.shape[0]
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)  # noqa: E731
+        out = dict(action=new(n, 6), unit=new(n, 6), logp=new(n))
+        if logits:
+            out["logits"] = new(n, 12)
+        rc = _abi.load().ctr_gauss_act(self._struct, _abi.ptr(rows), n, self.seed, int(counter) & 0xFFFFFFFFFFFFFFFF,
+                                       int(row_base), int(bool(deterministic)), _abi.ptr(out["action"]),
+                                       _abi.ptr(out["unit"]), _abi.ptr(out["logp"]), _abi.ptr(out.get("logits")),
+                                       _abi.stream_ptr(stream, self.device.index))
+        _abi.check(rc, "ctr_gauss_act")
+        return out
+
+
 def polyak_(nets, tau, stream=None):
     """The soft (Polyak) update of 1..4 target networks and the refresh of their device blobs in one
     launch (ctr_polyak).  ``nets``: a list of triples ``(net, online, target)``: ``net`` the device
@@ -520,7 +664,7 @@ def polyak_(nets, tau, stream=None):
     arr = (_abi_polyak.CtrPolyakNet * len(nets))()
     device, done = None, []
     for m, (net, online, target) in enumerate(nets):
-        if not isinstance(net, _Mlp):
+        if not isinstance(net, _Mlp) or isinstance(net, GaussianActor):
             raise ValueError("net %d must be an MlpActor or an MlpCritic" % m)
         on = net._device_layers(online, "net %d: online " % m)
         tg = net._device_layers(target, "net %d: target " % m, target=True)

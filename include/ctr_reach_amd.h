@@ -47,6 +47,11 @@
  *                       no counterpart in the reference, which trains DDPG: the TD3 variant of the two
  *                       (Fujimoto et al. 2018; stable-baselines' TD3 defaults): the clipped double-Q
  *                       target on a noise-smoothed target action, and both critics' regression
+ *   ctr_gauss_act / ctr_sac_actor_step
+ *                       no counterpart in the reference either: stable-baselines' third model class
+ *                       for a continuous action space, SAC (Haarnoja et al. 2018), with its defaults:
+ *                       the tanh-Gaussian policy's sample and log-probability, and the policy's update
+ *                       under the smaller of two critics with the learned temperature
  *   ctr_explore / ctr_collect
  *                       the data collection of the reference's training pipeline, stable-baselines
  *                       DDPG under HER: NormalActionNoise clipped to the action box and
@@ -907,6 +912,99 @@ int ctr_td3_critic_step(const ctr_critic_t *const critic[2], const ctr_ddpg_net_
                         const float *scale, const float *target, int64_t B,
                         float *loss /* device float[2] or NULL */,
                         void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * SAC (added within ABI 17: new symbols, no entry point or struct changes): a tanh-Gaussian policy
+ * on the device and the policy's update under two critics with a learned temperature.  The critics'
+ * regression is ctr_td3_critic_step, the target critics are ctr_critic, the soft update ctr_polyak.
+ *
+ * The Gaussian policy is the "MLP actor" above -- the same ctr_actor_t, limits, blob format and
+ * bf16 arithmetic -- with a 12-row output layer and no tanh on it: rows 0..5 are the mean, rows
+ * 6..11 the log standard deviation before clipping.  ctr_gauss_blob_bytes / ctr_gauss_pack (host) /
+ * ctr_gauss_load (device) are ctr_actor_blob_bytes / _pack / _load for W[n_hidden] [12][width] and
+ * b[n_hidden] [12]; the blob has the 6-row actor's size, and equals the blob of the actor built
+ * from the first six rows except in the bytes that hold rows 6..11.
+ *
+ * ctr_gauss_act: rows [n][in_dim] f32 (device) -> actions [n][6], unit [n][6], logp [n],
+ * logits [n][12] (device; each may be NULL).  In f32, every operation rounded once, no contraction:
+ *     y[0..11] = the head's f32 outputs (bias added: ctr_actor's logits of a 12-row layer)
+ *     s_i      = fminf(fmaxf(y[6+i], -20), 2)
+ *     eps_i    = six standard normals from two Philox4x32-10 blocks of stream 8, key = seed, counter
+ *                words {blk, (u32)counter, (u32)(row_base + row), (u32)(counter >> 32) ^ (8u << 24)},
+ *                blk = 0, 1: uniforms v_k = (word >> 8) * 2^-24 from words 0..3 of block 0 and 0..1
+ *                of block 1; for j = 0..2: r = sqrtf(-2 * logf(1 - v_2j)),
+ *                (sn, cs) = sincosf(6.2831855f * v_(2j+1)), eps_2j = r * cs, eps_(2j+1) = r * sn
+ *                (ctr_her_sample_td3's draw on another stream)
+ *     u_i      = fmaf(expf(s_i), eps_i, y[i]);  t_i = tanhf(u_i)
+ *     unit_i   = t_i;  action_i = scale_i * t_i
+ *     softplus(x) = fmaxf(x, 0) + log1pf(expf(-fabsf(x)))
+ *     logp     = sum over i = 0..5, in that order, of
+ *                ((-0.5f * (eps_i * eps_i) - s_i) - 0.9189385f) - 2 * ((0.6931472f - u_i) - softplus(-2 * u_i))
+ * deterministic != 0: u_i = y[i] and eps_i = 0 in logp; nothing is drawn.  A row's results are a
+ * pure function of the row, the weights and (seed, counter, row_base + row): they do not depend on
+ * n, on the other rows or on how a batch is split into calls.  One launch, nothing read back or
+ * allocated (it can be captured into a graph).  rows 0..5 of logits are ctr_actor's logits of the
+ * 6-row actor built from the first six rows, bit for bit, and the deterministic action is its action.
+ * Refused (CTR_EINVAL, before any HIP call): a NULL actor, a shape ctr_actor refuses, a scale that
+ * is not finite, a NULL or misaligned blob, n outside 0..2^31 - 1, row_base < 0 or row_base + n
+ * above 2^32, rows NULL where n > 0.
+ *
+ * ctr_sac_actor_step: one step of the policy (ctr_ddpg_net_t of the 12-row network) on rows
+ * [B][in_dim] under the two critics' current f32 parameters critic_W[y], critic_b[y], read only.
+ * The networks run in f32 as in ctr_ddpg_actor_step; eps is ctr_gauss_act's draw for (seed,
+ * counter, row) with row_base 0; the head between the policy and the critics runs in f64 on the f32
+ * logits and eps and is rounded to f32 where it meets the networks (the action t_i, the gradient
+ * of the logits):
+ *     alpha = exp(*log_alpha), read when the first launch starts
+ *     s, u, t, logp as above;  q_j = Q_j([row, t])
+ *     loss      = sum_r (alpha * logp_r - min(q_1r, q_2r)) * (1/B)         (a tie: critic 1)
+ *     logp_mean = sum_r logp_r * (1/B)
+ * backward: dL/dq = -1/B on the critic that gave the minimum and 0 on the other, through both
+ * critics to their six action inputs, summed; with dt_i that sum,
+ *     dL/du_i     = dt_i (1 - t_i^2) + (alpha/B) 2 t_i
+ *     dL/dy[i]    = dL/du_i
+ *     dL/dy[6+i]  = dL/du_i exp(s_i) eps_i - alpha/B     where -20 <= y[6+i] <= 2, else 0
+ * then through the policy.  The gradients go to gW, gb, the loss to *loss, logp_mean to *logp_mean
+ * (device, or NULL); the policy takes ctr_ddpg_actor_step's Adam step (tiles, slots, summation order
+ * and the step's arithmetic are that call's).  The temperature: alpha_state->state is device
+ * float[4] = {m, v, beta1^t, beta2^t} ({0, 0, 1, 1} before the first step); the gradient of
+ * -log_alpha * (logp_mean + target_entropy), g = -(logp_mean + target_entropy) in f32, goes to
+ * *alpha_state->grad (device, or NULL), and with learn != 0 *log_alpha takes the Adam step above
+ * with alpha_state->lr and adam's beta1, beta2, eps; with learn == 0 log_alpha and state are not
+ * written.  Two launches; the temperature's step is made by one thread of the second.
+ * workspace: device, 16-B aligned; ctr_sac_workspace_bytes(actor, critic1, critic2, max_B) serves
+ * this call and ctr_td3_critic_step on the same critics for every B <= max_B (-1 on a refused shape
+ * or max_B outside 1..65 536).
+ * LDS: a workgroup keeps one tile image of all three networks, 16 x (36 + sum (width + 4) + 20)
+ * floats each.  Every trio whose blobs fit CTR_ACTOR_MAX_BYTES fits (the largest image, of hidden
+ * [224, 64, 256], is 38.25 KB); a trio that did not would be refused with the byte counts in the
+ * message.
+ * Refused (CTR_EINVAL, before any HIP call, ctr_last_error names the function): whatever
+ * ctr_ddpg_actor_step refuses for the policy's net; a NULL array, entry or layer; critics whose
+ * in_dim is not actor->in_dim + 6; log_alpha, alpha_state or its state NULL; target_entropy or
+ * alpha_state->lr not finite; a critic tensor that is a tensor of the policy's net or an output;
+ * log_alpha, state, grad, loss, logp_mean, pow not distinct from each other, from the policy's
+ * tensors and from rows; the LDS limit; B outside 0..65 536 (B = 0 is a no-op). */
+typedef struct ctr_sac_alpha_t {
+    float *state;                   /* device float[4]: m, v, beta1^t, beta2^t               */
+    float *grad;                    /* device float, or NULL: the temperature's gradient     */
+    float lr;
+    int32_t learn;                  /* 0: log_alpha and state are never written              */
+} ctr_sac_alpha_t;
+int64_t ctr_gauss_blob_bytes(const ctr_actor_t *actor);
+int ctr_gauss_pack(const ctr_actor_t *actor, const float *const *W, const float *const *b, void *blob_host);
+int ctr_gauss_load(const ctr_actor_t *actor, const float *const *W, const float *const *b, void *stream);
+int ctr_gauss_act(const ctr_actor_t *actor, const float *rows, int64_t n, uint64_t seed, uint64_t counter,
+                  int64_t row_base, int32_t deterministic, float *actions, float *unit, float *logp,
+                  float *logits, void *stream);
+int64_t ctr_sac_workspace_bytes(const ctr_actor_t *actor, const ctr_critic_t *critic1,
+                                const ctr_critic_t *critic2, int64_t max_B);
+int ctr_sac_actor_step(const ctr_actor_t *actor, const ctr_ddpg_net_t *net, const ctr_ddpg_adam_t *adam,
+                       const ctr_critic_t *const critic[2], const float *const *const critic_W[2],
+                       const float *const *const critic_b[2], const float *rows, int64_t B, uint64_t seed,
+                       uint64_t counter, float *log_alpha, const ctr_sac_alpha_t *alpha_state,
+                       float target_entropy, float *loss, float *logp_mean, void *workspace,
+                       int64_t workspace_bytes, void *stream);
 
 /* CtrReachEnv.reset for the environments with mask[i] != 0 (mask NULL = all).
  * goal [n][3] or NULL (sample a goal), system [n] or NULL (sample uniformly).
