@@ -2,7 +2,10 @@
 and the small helpers): SAC's policy loss under CPU autograd in a chosen precision with the noise
 passed in, and ``case``: networks with torch's default init and a U(-1, 1) batch whose float64
 reference stays clear of the three places where a rounding would change the function -- a relu's
-kink, the minimum of the two critics, the clip of the log standard deviation."""
+kink, the minimum of the two critics, the clip of the log standard deviation; a batch kept clear of
+them row by row (``make_clear``), also under a saturated or clipped head; and the cases of
+tests/test_gpu_sac_edges.py."""
+import collections
 import copy
 import functools
 
@@ -130,3 +133,190 @@ def set_log_std_bias(policy, values):
             if v is not None:
                 W[6 + i].zero_()
                 b[6 + i] = float(v)
+
+
+# --- a batch clear of the kink, of Q1 = Q2 and of the clip's ends row by row ----------------------
+
+MIN_KINK, MIN_GAP, MIN_CLIP = 1e-5, 1e-4, 1e-3
+
+Clear = collections.namedtuple("Clear", "made eps redrawn passes ref64 ref32")
+Rows = collections.namedtuple("Rows", "kink gap clip first")
+
+
+def head64(policy, rows, eps):
+    """The policy's head in float64 numpy on noise ``eps`` [B, 6]: dict(raw: y[:, 6:] before the clip,
+    u, t = tanh(u), pre: the policy's hidden pre-activations)."""
+    y, pre, _ = R._forward64(R._np64(policy), rows.double().numpy(), False)
+    raw = y[:, 6:]
+    u = y[:, :6] + np.exp(np.clip(raw, LOG_STD_MIN, LOG_STD_MAX)) * np.asarray(eps, dtype=np.float64)
+    return dict(raw=raw, u=u, t=np.tanh(u), pre=pre)
+
+
+def row_conditions(policy, c1, c2, rows, eps, clip_dims=(0, 1, 2, 3, 4, 5)):
+    """Per row, in float64 numpy: Rows(kink: the smallest |hidden pre-activation| of the three networks,
+    gap: |Q1 - Q2|, clip: the smallest distance of a y[6 + i], i in ``clip_dims``, from -20 and 2, first:
+    critic 1 gives the minimum), the critics evaluated at the sampled tanh(u) of noise ``eps`` [B, 6].
+    Each row's values depend on that row and its own noise alone."""
+    head = head64(policy, rows, eps)
+    xa = np.concatenate((rows.double().numpy(), head["t"]), axis=1)
+    q1, pre1, _ = R._forward64(R._np64(c1), xa, False)
+    q2, pre2, _ = R._forward64(R._np64(c2), xa, False)
+    kink = np.min([np.abs(z).min(axis=1) for z in head["pre"] + pre1 + pre2], axis=0)
+    raw = head["raw"][:, list(clip_dims)]
+    clip = np.minimum(np.abs(raw - LOG_STD_MIN), np.abs(raw - LOG_STD_MAX)).min(axis=1)
+    return Rows(kink, np.abs(q1 - q2)[:, 0], clip, (q1 <= q2)[:, 0])
+
+
+def references(made, eps, alpha=ALPHA, target_entropy=TARGET_ENTROPY):
+    """``autograd``'s (float64, float32) references of ``made`` under noise ``eps``."""
+    import torch
+    return tuple(autograd(*made, eps, alpha, d, target_entropy) for d in (torch.float64, torch.float32))
+
+
+def make_clear(seed, p_hidden, c1_hidden, c2_hidden, in_dim, B, mean_gain=1.0, std_gain=1.0, std_bias=None, noise=(0, 0),
+               exact_ends=None, max_passes=20):
+    """``make``'s networks and batch with a shaped head: W and b of the policy's output rows 0..5 times
+    ``mean_gain`` and of rows 6..11 times ``std_gain``, ``std_bias`` (six values) added to b[6:], and
+    then ``exact_ends`` (six values or None each) as ``set_log_std_bias`` takes them: those log standard
+    deviations are that constant exactly, in float32 and in float64, and the clip condition below looks
+    at the other dimensions only.  The noise is ``eps_for(B, *noise)``, keyed by the row's index, so a
+    row drawn again keeps its noise.  Every row whose ``row_conditions`` are within 1e-5 of a kink, 1e-4
+    of Q1 = Q2 or 1e-3 of a clip end is drawn again from a generator of its own (seeded 5000 + seed),
+    pass after pass, until none is left: Clear(made, eps, redrawn, passes, ref64, ref32) with redrawn
+    the number of draws made again and ref64, ref32 ``autograd``'s references at ALPHA.  With all
+    gains 1 and nothing to draw again the batch is ``make``'s, bit for bit."""
+    import torch
+    policy, c1, c2, rows = make(seed, p_hidden, c1_hidden, c2_hidden, in_dim, B)
+    W, b = R.params(policy)[-1]
+    with torch.no_grad():
+        for part, gain in ((slice(0, 6), mean_gain), (slice(6, 12), std_gain)):
+            W[part] *= gain
+            b[part] *= gain
+        if std_bias is not None:
+            b[6:] += torch.tensor([float(v) for v in std_bias], dtype=b.dtype)
+    clip_dims = tuple(range(6))
+    if exact_ends is not None:
+        set_log_std_bias(policy, exact_ends)
+        clip_dims = tuple(i for i, v in enumerate(exact_ends) if v is None)
+    eps = eps_for(B, *noise)
+    g = torch.Generator().manual_seed(5000 + seed)
+    redrawn = passes = 0
+    while True:
+        c = row_conditions(policy, c1, c2, rows, eps, clip_dims)
+        bad = np.flatnonzero((c.kink < MIN_KINK) | (c.gap < MIN_GAP) | (c.clip < MIN_CLIP))
+        if not len(bad):
+            break
+        assert passes < max_passes, "%d rows near a kink, Q1 = Q2 or a clip end after %d passes" % (len(bad), passes)
+        passes += 1
+        redrawn += len(bad)
+        rows[torch.from_numpy(bad)] = torch.rand((len(bad), in_dim), generator=g) * 2 - 1
+    made = (policy, c1, c2, rows)
+    return Clear(made, eps, redrawn, passes, *references(made, eps))
+
+
+@functools.lru_cache(maxsize=None)
+def case_clear(p_hidden, c1_hidden, c2_hidden, in_dim, B, mean_gain=1.0, std_gain=1.0, std_bias=None, noise=(0, 0),
+               exact_ends=None, seed=0):
+    """``make_clear`` computed once per case."""
+    return make_clear(seed, p_hidden, c1_hidden, c2_hidden, in_dim, B, mean_gain, std_gain, std_bias, noise, exact_ends)
+
+
+def clip_min(clear, dims=(0, 1, 2, 3, 4, 5)):
+    """The smallest distance of a y[6 + i], i in ``dims``, from the clip's ends over a Clear's batch."""
+    return float(row_conditions(*clear.made, clear.eps, dims).clip.min())
+
+
+def saturation(clear):
+    """Of the (row, dimension) pairs of a Clear's float64 head: (the fraction whose float32(tanh(u)) is
+    exactly +-1, the fraction with |tanh(u)| < 0.9)."""
+    t = head64(clear.made[0], clear.made[3], clear.eps)["t"]
+    return float((np.abs(t.astype(np.float32)) == 1).mean()), float((np.abs(t) < 0.9).mean())
+
+
+def clipping(clear):
+    """Of all y[6 + i] of a Clear's float64 head: (the fraction above 2, the fraction below -20, the open
+    fraction, whether each of the six dimensions has both open and clipped rows)."""
+    raw = head64(clear.made[0], clear.made[3], clear.eps)["raw"]
+    above, below = raw > LOG_STD_MAX, raw < LOG_STD_MIN
+    is_open = ~(above | below)
+    return (float(above.mean()), float(below.mean()), float(is_open.mean()),
+            bool((is_open.any(axis=0) & (~is_open).any(axis=0)).all()))
+
+
+# The cases of tests/test_gpu_sac_edges.py, whose conditions tests/test_host_sac_ref.py checks without a GPU
+# (all with seed 0).  A: past T * SLOTS rows with a ragged tile on the shapes test_gpu_sac_grads.py does not take there;
+# 2 101 = 2 * 1 024 + 3 * 16 + 5: two tiles in every slot, a third in the first four, the last one ragged; and max_B
+# with 64 whole tiles in every slot.  On SHAPES[2] and SHAPES[3] critic 1 gives the minimum on every row at seed 0.
+TILES_CASES = [(shape, T * SLOTS + 5) for shape in SHAPES[1:]]
+TILES_CASES += [(SHAPES[0], 2 * T * SLOTS + 53), (SHAPES[1], 2 * T * SLOTS + 53), (SHAPES[0], 65536)]
+TILES_MIXED = (SHAPES[0], SHAPES[1])                 # on these critic 1's share must be 0.1 .. 0.9
+MAX_REDRAWN, MAX_PASSES = 0.05, 20
+MEAN_GAIN = 100.0                                    # B: of the saturated head's mean rows
+SATURATED_CASES = [(SHAPES[1], 70), (SHAPES[1], T * SLOTS + 5), (SHAPES[2], 70)]
+STD_GAIN, STD_BIAS = 8.0, (1.5, 1.5, 1.5, -19.0, -19.0, -19.0)    # C: some rows clipped and some open in every dimension
+CLIP_CASES = [(SHAPES[0], 70), (SHAPES[3], T * SLOTS + 5)]
+# D: the log standard deviations 0..3 sit on the clip's two ends and one float32 outside each
+ENDS = (2.0, -20.0, float(np.nextafter(np.float32(2.0), np.float32(np.inf))),
+        float(np.nextafter(np.float32(-20.0), np.float32(-np.inf))), None, None)
+ENDS_CASE = (SHAPES[1], 70)
+# E: a seed and a counter whose halves differ, so that neither swapping them nor dropping their high words goes unseen
+DRAW_SEED, DRAW_COUNTER = (7 << 32) | 3, (5 << 32) | 11
+DRAW_CASE = (SHAPES[0], 70)
+# F: the temperature moves between two steps of one draw
+TEMP_CASE, TEMP_COUNTER, TEMP_ALPHA_LR, TEMP_TARGET = (SHAPES[0], 70), 4, 1e-2, -3.5
+
+
+def tiles_case(shape, B):
+    return case_clear(*shape, B)
+
+
+def saturated_case(shape, B):
+    return case_clear(*shape, B, mean_gain=MEAN_GAIN)
+
+
+def clip_case(shape, B):
+    return case_clear(*shape, B, std_gain=STD_GAIN, std_bias=STD_BIAS)
+
+
+def ends_case():
+    return case_clear(*ENDS_CASE[0], ENDS_CASE[1], exact_ends=ENDS)
+
+
+Draw = collections.namedtuple("Draw", "clear second")
+
+
+@functools.lru_cache(maxsize=None)
+def draw_case():
+    """E: Draw(the Clear of noise (DRAW_SEED, DRAW_COUNTER), (eps, ref64, ref32) of the same batch under
+    (DRAW_SEED, DRAW_COUNTER + 1)): what two consecutive steps of a learner with that seed and count see."""
+    clear = case_clear(*DRAW_CASE[0], DRAW_CASE[1], noise=(DRAW_SEED, DRAW_COUNTER))
+    eps = eps_for(DRAW_CASE[1], DRAW_SEED, DRAW_COUNTER + 1)
+    return Draw(clear, (eps,) + references(clear.made, eps))
+
+
+def wrong_draws(seed, counter):
+    """The (seed, counter) pairs a faulty call would draw with in place of (seed, counter): the two
+    swapped, and the low 32 bits of each."""
+    return {"swapped": (counter, seed), "low words": (seed & 0xFFFFFFFF, counter & 0xFFFFFFFF)}
+
+
+@functools.lru_cache(maxsize=None)
+def temperature_case():
+    """F: the Clear of noise (0, TEMP_COUNTER) with its references at ALPHA and TEMP_TARGET."""
+    clear = case_clear(*TEMP_CASE[0], TEMP_CASE[1], noise=(0, TEMP_COUNTER))
+    return clear._replace(**dict(zip(("ref64", "ref32"), references(clear.made, clear.eps, ALPHA, TEMP_TARGET))))
+
+
+def bars(ref64, ref32, target_entropy=TARGET_ENTROPY, floor=2.0 ** -23):
+    """The bar of every quantity a step is held to, from torch's float32 CPU autograd against float64's:
+    dict(loss, logp_mean: 8 times torch's relative error, at least ``floor`` (float32's spacing is between
+    2^-24 and 2^-23 of the value); alpha_grad: an absolute error, 8 times torch's, at least ``floor`` times
+    the larger addend of the float32 sum -(logp_mean + target_entropy); grads: [(gW's, gb's), ...], 8
+    times torch's max|g - g64| / max|g64|, no floor) and the same dict of torch's own errors."""
+    theirs = {name: abs(ref32[name] - ref64[name]) / abs(ref64[name]) for name in ("loss", "logp_mean")}
+    theirs["alpha_grad"] = abs(ref32["alpha_grad"] - ref64["alpha_grad"])
+    theirs["grads"] = [tuple(err(g32, g64) for g32, g64 in zip(p32, p64)) for p32, p64 in zip(ref32["grads"], ref64["grads"])]
+    bar = {name: max(8 * theirs[name], floor) for name in ("loss", "logp_mean")}
+    bar["alpha_grad"] = max(8 * theirs["alpha_grad"], floor * max(abs(ref64["logp_mean"]), abs(target_entropy)))
+    bar["grads"] = [tuple(8 * e for e in pair) for pair in theirs["grads"]]
+    return bar, theirs
