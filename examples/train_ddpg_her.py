@@ -68,6 +68,13 @@ critics and the temperature's), ``pi_dev.load_(policy)`` and one ``polyak_`` of 
 defaults with ``ent_coef='auto'``.  ``pi_dev.mean_actor()`` gives the trained policy's deterministic mean
 to ``venv.rollout`` / ``follow`` for evaluation.
 
+With ``--sac --device-targets`` (``main(..., sac=True, device_targets=True)``) the first four of those
+steps are one call: ``her.sample_sac(batch_size, pi_dev, targets_dev[0], targets_dev[1], GAMMA,
+learner.log_alpha)`` returns the batch with ``target``, made in the sampler's launch from the current
+policy's sample on ``next_obs``, the two target critics and the temperature read on the device.  The
+noise is keyed by the replay draw itself, whose seed is not the collection's, so no counter offset is
+needed.
+
 usage: python examples/train_ddpg_her.py [--num-envs N] [--iterations I] [--steps-per-iter S]
            [--batch-size B] [--updates-per-iter U] [--hidden 64,64] [--seed 0] [--device cuda]
            [--device-targets] [--device-polyak] [--device-update] [--td3] [--sac]"""
@@ -108,7 +115,8 @@ def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, update
     if sac and td3:
         raise ValueError("--sac and --td3 are two algorithms: choose one")
     if sac:
-        return main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter, hidden, seed, device)
+        return main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter, hidden, seed, device,
+                        device_targets)
     device = torch.device(device)
     device_update = device_update or td3
     device_polyak = device_polyak or device_update
@@ -225,7 +233,8 @@ def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, update
                 rollout_stats=venv.rollout_stats, venv=venv, her=her)
 
 
-def main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter, hidden, seed, device):
+def main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter, hidden, seed, device,
+             device_targets=False):
     """``main(..., sac=True)``: the same loop with SAC's pieces (the module docstring)."""
     device = torch.device(device)
     torch.manual_seed(seed)
@@ -255,12 +264,17 @@ def main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter,
         critic_sum = torch.zeros((), device=device)
         policy_sum = torch.zeros((), device=device)
         for _ in range(updates_per_iter):
-            batch = her.sample(batch_size)
-            # the sampling draws and the collection draws share the key: keep their counters apart
-            nxt = pi_dev.sample(batch["next_obs"], counter=(1 << 40) + update)
-            update += 1
-            q = torch.minimum(targets_dev[0](batch["next_obs"], nxt["unit"]), targets_dev[1](batch["next_obs"], nxt["unit"]))
-            target = batch["reward"] + GAMMA * (1.0 - batch["done"]) * (q - learner.alpha * nxt["logp"])
+            if device_targets:                                               # the batch and its soft target: one call
+                batch = her.sample_sac(batch_size, pi_dev, targets_dev[0], targets_dev[1], GAMMA, learner.log_alpha)
+                target = batch["target"]
+            else:
+                batch = her.sample(batch_size)
+                # the sampling draws and the collection draws share the key: keep their counters apart
+                nxt = pi_dev.sample(batch["next_obs"], counter=(1 << 40) + update)
+                update += 1
+                q = torch.minimum(targets_dev[0](batch["next_obs"], nxt["unit"]),
+                                  targets_dev[1](batch["next_obs"], nxt["unit"]))
+                target = batch["reward"] + GAMMA * (1.0 - batch["done"]) * (q - learner.alpha * nxt["logp"])
             learner.critic_step(batch["obs"], batch["action"], target)
             learner.actor_step(batch["obs"])
             pi_dev.load_(policy)
@@ -284,7 +298,9 @@ if __name__ == "__main__":
     ap.add_argument("--hidden", default="64,64", help="hidden widths, multiples of 32")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda")
-    ap.add_argument("--device-targets", action="store_true", help="the DDPG target from her.sample_td (bf16 target networks)")
+    ap.add_argument("--device-targets", action="store_true",
+                    help="the DDPG target from her.sample_td (bf16 target networks); with --sac the soft target from "
+                         "her.sample_sac")
     ap.add_argument("--device-polyak", action="store_true",
                     help="the Polyak update and both blob refreshes in one polyak_ launch (implies --device-targets)")
     ap.add_argument("--device-update", action="store_true",

@@ -55,10 +55,12 @@ __device__ __forceinline__ float td_target(float rew, float dn, float gamma, flo
 // td_next_action: the sampler's row, the flush of the batch and a' = tanhf(the actor's logits) on
 // the lane's next_obs row (row[20], as critic_row takes it).  The actor's blob is still in use by
 // other waves when it returns: a barrier comes before the region is staged again.
-__device__ __forceinline__ void td_next_action(const ctr_her_t &h, int64_t B, uint64_t seed, uint64_t counter,
-                                               const ctr_her_batch_t &out, const ActorK &ak, char *lds, float *s_obs,
-                                               float *s_nobs, float *s_act, float &rew, float &dn, float row[20],
-                                               float a[6])
+//
+// td_next_row is its first half, which ctr_sac.inc's k_her_sample_sac shares: the sampler's row, the
+// policy's blob staged beside it, the flush of the batch and the lane's next_obs row in registers.
+__device__ __forceinline__ void td_next_row(const ctr_her_t &h, int64_t B, uint64_t seed, uint64_t counter,
+                                            const ctr_her_batch_t &out, const ActorK &ak, char *lds, float *s_obs,
+                                            float *s_nobs, float *s_act, float &rew, float &dn, float row[20])
 {
     her_sample_row(h, B, seed, counter, out, s_obs, s_nobs, s_act, rew, dn);
     actor_stage(ak, lds);
@@ -66,10 +68,18 @@ __device__ __forceinline__ void td_next_action(const ctr_her_t &h, int64_t B, ui
     her_flush_batch(h, B, out, s_obs, s_nobs, s_act);
     const bool multi = h.obs_dim == 14;
     const float *sn = s_nobs + threadIdx.x * (h.obs_dim + 6);     // the f32 row as stored to out.next_obs
-    float y[6];
     #pragma unroll
     for (int k = 0; k < 19; ++k) row[k] = sn[k];
     row[19] = multi ? sn[19] : 0.f;
+}
+
+__device__ __forceinline__ void td_next_action(const ctr_her_t &h, int64_t B, uint64_t seed, uint64_t counter,
+                                               const ctr_her_batch_t &out, const ActorK &ak, char *lds, float *s_obs,
+                                               float *s_nobs, float *s_act, float &rew, float &dn, float row[20],
+                                               float a[6])
+{
+    td_next_row(h, B, seed, counter, out, ak, lds, s_obs, s_nobs, s_act, rew, dn, row);
+    float y[6];
     actor_logits(ak, lds, row, y);
     #pragma unroll
     for (int i = 0; i < 6; ++i) a[i] = tanhf(y[i]);

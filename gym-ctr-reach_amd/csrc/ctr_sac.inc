@@ -1,4 +1,4 @@
-// ctr_sac.inc -- SAC's two device pieces (include/ctr_reach_amd.h, "SAC": the specification), with
+// ctr_sac.inc -- SAC's three device pieces (include/ctr_reach_amd.h, "SAC": the specification), with
 // their extern "C" entry points.  Included at the end of ctr_kernels.hip, after ctr_ddpg.inc.
 //
 // ctr_gauss_act: the tanh-Gaussian policy.  ctr_actor's MLP (actor_tile, the bf16 blob) with a 12-row
@@ -13,6 +13,10 @@
 // policy and the critics, and the minimum of the two critics in the loss; the layers, the tiles, the
 // slots and their order are ctr_ddpg.inc's device functions.  k_sac_apply is ddpg_apply_element
 // (k_ddpg_apply's body) plus one thread that makes the temperature's step.
+//
+// ctr_her_sample_sac: the replay draw with SAC's soft target.  k_her_sample_sac is k_her_sample_td3
+// (ctr_critic.inc: td_next_row, td_critic, td_target) with gauss_logits, gauss_eps and gauss_head
+// in the target policy's place.
 namespace {
 
 int gauss_layout(const ctr_actor_t *a, ActorK *ak)
@@ -121,6 +125,61 @@ __global__ __launch_bounds__(BLOCK) void k_gauss_act(ActorK ak, const float *__r
     if (g.logits)
         #pragma unroll
         for (int i = 0; i < 12; ++i) g.logits[12 * e + i] = y[i];
+}
+
+// ------------------------------------------------------------------------------------------
+// The soft target inside the sampler.  Kernel-argument copy of ctr_her_sac_t.
+struct HerSacK {
+    float gamma;
+    const float *log_alpha;
+    float *target, *q1_next, *q2_next, *next_action, *next_logp;
+};
+
+// min(q1, q2) - alpha logp as two f32 roundings: numpy's float32 np.minimum(q1, q2) - alpha * logp, bit for bit.
+__device__ __forceinline__ float sac_soft_q(float q1, float q2, float alpha, float lp)
+{
+#pragma clang fp contract(off)
+    const float al = alpha * lp;
+    return fminf(q1, q2) - al;
+}
+
+// k_her_sample_td3 (ctr_critic.inc) with SAC's target: the CURRENT policy's stochastic head on the
+// next_obs row the lane just staged, drawn under the sampler's own (seed, counter) -- k_gauss_act's
+// draw for row_base 0 --, then the two target critics, one after the other in the same LDS region,
+// and the smaller q less alpha logp in the target.  Wave-uniform around the MFMA code, as there:
+// the lanes past B compute on their zero rows, and only the stores are guarded.
+__global__ __launch_bounds__(BLOCK) void k_her_sample_sac(HerK hk, int64_t B, uint64_t seed, uint64_t counter,
+                                                          ctr_her_batch_t out, ActorK ak, ActorK ck1, ActorK ck2, HerSacK td)
+{
+    __shared__ __attribute__((aligned(16))) float s_obs[BLOCK * HER_DMAX];
+    __shared__ __attribute__((aligned(16))) float s_nobs[BLOCK * HER_DMAX];
+    __shared__ __attribute__((aligned(16))) float s_act[BLOCK * 6];
+    const ctr_her_t &h = hk.h;
+    float rew, dn, row[20];
+    char *lds = actor_lds_base(0);
+    td_next_row(h, B, seed, counter, out, ak, lds, s_obs, s_nobs, s_act, rew, dn, row);
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    float y[12], eps[6], t[6];
+    gauss_logits(ak, lds, row, y);
+    gauss_eps(seed, counter, (uint32_t)i, eps);
+    const float lp = gauss_head(y, eps, false, t);
+    const bool multi = h.obs_dim == 14;
+    __syncthreads();                                      // every wave is through with the policy's blob
+    const float q1 = td_critic(ck1, lds, row, t, multi);
+    __syncthreads();                                      // ... and with the first critic's
+    const float q2 = td_critic(ck2, lds, row, t, multi);
+    const float alpha = (float)exp((double)*td.log_alpha);          // a uniform load; f64 so that the host can restate it
+    const float soft = sac_soft_q(q1, q2, alpha, lp);
+    const float tg = td_target(rew, dn, td.gamma, soft);
+    if (i < B) {
+        td.target[i] = tg;
+        if (td.q1_next) td.q1_next[i] = q1;
+        if (td.q2_next) td.q2_next[i] = q2;
+        if (td.next_logp) td.next_logp[i] = lp;
+        if (td.next_action)
+            #pragma unroll
+            for (int k = 0; k < 6; ++k) td.next_action[6 * i + k] = t[k];
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -355,6 +414,41 @@ int ctr_gauss_act(const ctr_actor_t *a, const float *rows, int64_t n, uint64_t s
     const GaussK g = {seed, counter, (uint64_t)row_base, deterministic, actions, unit, logp, logits};
     hipLaunchKernelGGL(k_gauss_act, dim3(grid_for(n)), dim3(BLOCK), shm, (hipStream_t)stream, ak, rows, n, g);
     return hip_check("ctr_gauss_act launch");
+}
+
+int ctr_her_sample_sac(const ctr_her_t *her, int64_t batch_size, uint64_t seed, uint64_t counter,
+                       const ctr_her_batch_t *out, const ctr_her_sac_t *td, void *stream)
+{
+    const char *fn = "ctr_her_sample_sac";
+    int64_t tiles = 0;
+    // (batch_size <= 2^31 - 1 here, so the row index fits the noise key's 32-bit word)
+    if (int r = td_named(fn, her_sample_check(fn, her, batch_size, out, &tiles))) return r;
+    if (!td) return ddpg_fail(fn, "td is NULL");
+    ActorK ak, ck1, ck2;
+    if (int r = td_named(fn, gauss_layout(td->actor, &ak))) return r;          // (the scale is not read)
+    if (int r = td_named(fn, mlp_blob("actor", td->actor->blob, &ak))) return r;
+    if (!td->critic1 || !td->critic2) return ddpg_fail(fn, "critic1 or critic2 is NULL");
+    if (int r = td_named(fn, critic_check(td->critic1, &ck1))) return r;
+    if (int r = td_named(fn, critic_check(td->critic2, &ck2))) return r;
+    if (ak.in_dim != her->obs_dim + 6) return ddpg_fail(fn, "actor->in_dim must be her->obs_dim + 6");
+    if (ck1.in_dim != her->obs_dim + 12 || ck2.in_dim != her->obs_dim + 12)
+        return ddpg_fail(fn, "critic1->in_dim and critic2->in_dim must be her->obs_dim + 12");
+    if (!isfinite(td->gamma)) return ddpg_fail(fn, "gamma must be finite");
+    if (!td->log_alpha) return ddpg_fail(fn, "td->log_alpha is NULL");
+    if (!td->target) return ddpg_fail(fn, "td->target is NULL");
+    if (batch_size == 0) return 0;
+    // the row staging is the kernel's static LDS; the largest of the three blobs is the dynamic region
+    constexpr size_t fixed = (size_t)BLOCK * (2 * HER_DMAX + 6) * sizeof(float);
+    static_assert(fixed + CTR_ACTOR_MAX_BYTES + ACTOR_LDS_SLACK <= LDS_PER_WORKGROUP,
+                  "every policy and every critic fit beside the row staging");
+    const size_t shm = std::max(ak.bytes, std::max(ck1.bytes, ck2.bytes)) + ACTOR_LDS_SLACK;
+    if (int r = allow_dynamic_lds(k_her_sample_sac, shm)) return r;
+    const HerSacK tk = {td->gamma, td->log_alpha, td->target, td->q1_next, td->q2_next, td->next_action, td->next_logp};
+    hipLaunchKernelGGL(k_her_scan_tiles, dim3((unsigned)tiles), dim3(BLOCK), 0, (hipStream_t)stream, HerK{*her});
+    hipLaunchKernelGGL(k_her_scan_tops, dim3(1), dim3(BLOCK), 0, (hipStream_t)stream, HerK{*her}, tiles);
+    hipLaunchKernelGGL(k_her_sample_sac, dim3(grid_for(batch_size)), dim3(BLOCK), shm, (hipStream_t)stream, HerK{*her},
+                       batch_size, seed, counter, *out, ak, ck1, ck2, tk);
+    return hip_check("ctr_her_sample_sac launch");
 }
 
 int64_t ctr_sac_workspace_bytes(const ctr_actor_t *actor, const ctr_critic_t *critic1, const ctr_critic_t *critic2,

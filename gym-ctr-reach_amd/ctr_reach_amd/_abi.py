@@ -234,7 +234,7 @@ EXPORTED = ("ctr_abi_version", "ctr_last_error", "ctr_fk", "ctr_set_action", "ct
             "ctr_critic_pack", "ctr_critic_load", "ctr_critic", "ctr_her_sample_td", "ctr_polyak",
             "ctr_ddpg_workspace_bytes", "ctr_ddpg_critic_step", "ctr_ddpg_actor_step", "ctr_her_sample_td3",
             "ctr_td3_workspace_bytes", "ctr_td3_critic_step", "ctr_gauss_blob_bytes", "ctr_gauss_pack", "ctr_gauss_load",
-            "ctr_gauss_act", "ctr_sac_workspace_bytes", "ctr_sac_actor_step")
+            "ctr_gauss_act", "ctr_sac_workspace_bytes", "ctr_sac_actor_step", "ctr_her_sample_sac")
 
 _lib = None
 
@@ -327,7 +327,7 @@ def load(path=None):
         from . import _abi_td3                     # ctr_her_td3_t and the three prototypes
         _abi_td3.bind(L)
     if hasattr(L, "ctr_sac_actor_step"):           # added within ABI 17 (an older build lacks them)
-        from . import _abi_sac                     # ctr_sac_alpha_t and the six prototypes
+        from . import _abi_sac                     # ctr_sac_alpha_t, ctr_her_sac_t and the prototypes
         _abi_sac.bind(L)
     if hasattr(L, "ctr_ik_dls"):                   # ABI 17
         L.ctr_ik_dls.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrIk), _P]

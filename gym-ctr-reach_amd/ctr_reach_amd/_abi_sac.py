@@ -1,10 +1,10 @@
-"""ctypes mirror of ctr_sac_alpha_t and the prototypes of ctr_gauss_blob_bytes, ctr_gauss_pack,
-ctr_gauss_load, ctr_gauss_act, ctr_sac_workspace_bytes and ctr_sac_actor_step
-(include/ctr_reach_amd.h, "SAC": added within ABI 17).  ``_abi.load`` binds them;
-tests/test_host_sac.py checks the mirror against the header."""
+"""ctypes mirrors of ctr_sac_alpha_t and ctr_her_sac_t and the prototypes of ctr_gauss_blob_bytes,
+ctr_gauss_pack, ctr_gauss_load, ctr_gauss_act, ctr_sac_workspace_bytes, ctr_sac_actor_step and
+ctr_her_sample_sac (include/ctr_reach_amd.h, "SAC": added within ABI 17).  ``_abi.load`` binds them;
+tests/test_host_sac.py and tests/test_host_sac_target.py check the mirrors against the header."""
 import ctypes
 
-from ._abi import CtrActor, _P
+from ._abi import CtrActor, CtrHer, CtrHerBatch, _P
 from ._abi_critic import CtrCritic
 from ._abi_ddpg import CtrDdpgAdam, CtrDdpgNet
 from ._abi_td3 import CriticPair
@@ -13,6 +13,15 @@ from ._abi_td3 import CriticPair
 class CtrSacAlpha(ctypes.Structure):
     """ctr_sac_alpha_t: the temperature's Adam state, gradient, learning rate and switch."""
     _fields_ = [("state", _P), ("grad", _P), ("lr", ctypes.c_float), ("learn", ctypes.c_int32)]
+
+
+class CtrHerSac(ctypes.Structure):
+    """ctr_her_sac_t: the current policy, the target critics, the temperature and the outputs of
+    ctr_her_sample_sac."""
+    _fields_ = [("actor", ctypes.POINTER(CtrActor)), ("critic1", ctypes.POINTER(CtrCritic)),
+                ("critic2", ctypes.POINTER(CtrCritic)), ("log_alpha", _P), ("gamma", ctypes.c_float),
+                ("pad", ctypes.c_int32), ("target", _P), ("q1_next", _P), ("q2_next", _P), ("next_action", _P),
+                ("next_logp", _P)]
 
 
 LayersPair = ctypes.POINTER(_P) * 2                # const float *const *const critic_W[2]
@@ -31,3 +40,6 @@ def bind(L):
     L.ctr_sac_actor_step.argtypes = [A, ctypes.POINTER(CtrDdpgNet), ctypes.POINTER(CtrDdpgAdam), ctypes.POINTER(CriticPair),
                                      ctypes.POINTER(LayersPair), ctypes.POINTER(LayersPair), _P, i64, u64, u64, _P,
                                      ctypes.POINTER(CtrSacAlpha), ctypes.c_float, _P, _P, _P, i64, _P]
+    if hasattr(L, "ctr_her_sample_sac"):           # (a build from before the symbol lacks it)
+        L.ctr_her_sample_sac.argtypes = [ctypes.POINTER(CtrHer), i64, u64, u64, ctypes.POINTER(CtrHerBatch),
+                                         ctypes.POINTER(CtrHerSac), _P]

@@ -220,3 +220,69 @@ class HerReplayBuffer(object):
         _abi.check(rc, "ctr_her_sample_td3")
         self._counter += 1
         return out
+
+    def sample_sac(self, batch_size, policy, critic1, critic2, gamma, log_alpha, seed=None, stream=None,
+                   return_index=False, return_next=False):
+        """``sample`` with SAC's soft target of the drawn rows (ctr_her_sample_sac): the same dict, plus
+        target [B] = reward + gamma * (1 - done) * (min(Q1', Q2')(next_obs, a') - alpha * logp(a')) with
+        a' the CURRENT ``policy``'s stochastic action on next_obs in the normalised box (a
+        ``GaussianActor``; its scale is not applied and its own seed is not used), the two target
+        critics (``MlpCritic``; they may be the same object) and alpha = exp(log_alpha), all on this
+        buffer's device.  ``log_alpha``: a 0-d or 1-element float32 tensor on the buffer's device
+        (``SacLearner.log_alpha``), passed by pointer and read by the kernel when it runs, never on the
+        host; anything that would need a conversion or a copy is refused with ValueError.  With
+        ``return_next`` also q1_next [B], q2_next [B], next_action [B, 6] = a' and next_logp [B].
+
+        The noise of a' is keyed by this draw's own (seed, counter): it is ``GaussianActor(...,
+        seed=<the draw seed>).sample(next_obs, counter=<the draw's counter>, row_base=0)``, bit for
+        bit.  ``_draw_seed`` already keeps that key apart from the collection's, so the caller needs
+        no counter offsets.  One draw: the counter advances by one, as in ``sample``.  Asynchronous."""
+        from . import _abi_sac
+        from .policy import GaussianActor, MlpCritic
+        torch = _torch()
+        dev = self.venv.device
+
+        def elsewhere(d):
+            return d.type != dev.type or (None not in (d.index, dev.index) and d.index != dev.index)
+
+        if not isinstance(log_alpha, torch.Tensor):
+            raise ValueError("sample_sac: log_alpha must be a torch tensor on the buffer's device (it is read there)")
+        if elsewhere(log_alpha.device):
+            raise ValueError("sample_sac: log_alpha is on %s, the buffer on %s" % (log_alpha.device, dev))
+        if log_alpha.dtype != torch.float32:
+            raise ValueError("sample_sac: log_alpha must be float32, not %s" % log_alpha.dtype)
+        if log_alpha.dim() > 1 or log_alpha.numel() != 1:
+            raise ValueError("sample_sac: log_alpha must be a 0-d or 1-element tensor, not %s" % list(log_alpha.shape))
+        if not isinstance(policy, GaussianActor):
+            raise ValueError("sample_sac: the policy must be a GaussianActor (the 12-row head), not %s"
+                             % type(policy).__name__)
+        for net, name in ((critic1, "critic1"), (critic2, "critic2")):
+            if not isinstance(net, MlpCritic):
+                raise ValueError("sample_sac: the %s must be an MlpCritic, not %s" % (name, type(net).__name__))
+        for net, name in ((policy, "policy"), (critic1, "critic1"), (critic2, "critic2")):
+            if getattr(net, "blob", None) is None:
+                raise ValueError("sample_sac: the %s must be on the device" % name)
+            if elsewhere(net.device):
+                raise ValueError("sample_sac: the %s is on %s, the buffer on %s" % (name, net.device, dev))
+        gamma = float(gamma)
+        if not np.isfinite(gamma):
+            raise ValueError("sample_sac: gamma must be finite")
+        B, out, hb = self._batch(batch_size, return_index)
+        out["target"] = torch.empty(B, dtype=torch.float32, device=dev)
+        if return_next:
+            out["q1_next"] = torch.empty(B, dtype=torch.float32, device=dev)
+            out["q2_next"] = torch.empty(B, dtype=torch.float32, device=dev)
+            out["next_action"] = torch.empty((B, 6), dtype=torch.float32, device=dev)
+            out["next_logp"] = torch.empty(B, dtype=torch.float32, device=dev)
+        td = _abi_sac.CtrHerSac()
+        td.actor, td.critic1, td.critic2 = (ctypes.pointer(policy._struct), ctypes.pointer(critic1._struct),
+                                            ctypes.pointer(critic2._struct))
+        td.log_alpha, td.gamma = log_alpha.data_ptr(), gamma
+        td.target, td.q1_next, td.q2_next = _abi.ptr(out["target"]), _abi.ptr(out.get("q1_next")), _abi.ptr(out.get("q2_next"))
+        td.next_action, td.next_logp = _abi.ptr(out.get("next_action")), _abi.ptr(out.get("next_logp"))
+        rc = self.lib.ctr_her_sample_sac(self._h, B, self._draw_seed(seed), self._counter, hb, td,
+                                         _abi.stream_ptr(stream, self.venv.device.index))
+        _abi.check(rc, "ctr_her_sample_sac")
+        self._log_alpha = log_alpha        # stays referenced until the next draw: the launch reads it
+        self._counter += 1
+        return out

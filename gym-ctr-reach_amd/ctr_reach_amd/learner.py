@@ -419,16 +419,15 @@ class SacLearner(object):
     them; all given as ``DdpgLearner`` takes its networks.
 
         learner = SacLearner(policy, critic1, critic2, scale=venv.action_space.high)
-        batch = her.sample(256)
-        nxt = pi.sample(batch["next_obs"], counter)
-        q = torch.minimum(critic1_targ_dev(batch["next_obs"], nxt["unit"]), critic2_targ_dev(batch["next_obs"], nxt["unit"]))
-        target = batch["reward"] + gamma * (1 - batch["done"]) * (q - learner.alpha * nxt["logp"])
-        learner.critic_step(batch["obs"], batch["action"], target)
+        batch = her.sample_sac(256, pi, critic1_targ_dev, critic2_targ_dev, gamma, learner.log_alpha)
+        learner.critic_step(batch["obs"], batch["action"], batch["target"])
         learner.actor_step(batch["obs"])
         pi.load_(policy)
         polyak_([(critic1_targ_dev, critic1, critic1_targ), (critic2_targ_dev, critic2, critic2_targ)], 0.005)
 
-    ``critic_step`` is ``Td3Learner.critic_step`` (the same C call).  ``actor_step`` (ctr_sac_actor_step,
+    ``sample_sac`` (ctr_her_sample_sac) draws the batch and makes target = r + gamma (1 - done) (min(Q1',
+    Q2')(s', a') - alpha logp(a')) with a' from the current policy ``pi``, in the sampler's launch; it
+    reads ``log_alpha`` on the device.  ``critic_step`` is ``Td3Learner.critic_step`` (the same C call).  ``actor_step`` (ctr_sac_actor_step,
     two launches) samples an action per row from the policy with the noise of (``seed``, ``counter``,
     the row's index), and descends mean(alpha * logp - min(Q1, Q2)) through both critics, the tanh and
     the reparametrisation; with ``learn_alpha`` the temperature's ``log_alpha`` then takes its own Adam

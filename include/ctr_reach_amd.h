@@ -47,11 +47,12 @@
  *                       no counterpart in the reference, which trains DDPG: the TD3 variant of the two
  *                       (Fujimoto et al. 2018; stable-baselines' TD3 defaults): the clipped double-Q
  *                       target on a noise-smoothed target action, and both critics' regression
- *   ctr_gauss_act / ctr_sac_actor_step
+ *   ctr_gauss_act / ctr_sac_actor_step / ctr_her_sample_sac
  *                       no counterpart in the reference either: stable-baselines' third model class
  *                       for a continuous action space, SAC (Haarnoja et al. 2018), with its defaults:
- *                       the tanh-Gaussian policy's sample and log-probability, and the policy's update
- *                       under the smaller of two critics with the learned temperature
+ *                       the tanh-Gaussian policy's sample and log-probability, the policy's update
+ *                       under the smaller of two critics with the learned temperature, and the
+ *                       entropy-regularised target together with the replay draw that feeds it
  *   ctr_explore / ctr_collect
  *                       the data collection of the reference's training pipeline, stable-baselines
  *                       DDPG under HER: NormalActionNoise clipped to the action box and
@@ -1005,6 +1006,47 @@ int ctr_sac_actor_step(const ctr_actor_t *actor, const ctr_ddpg_net_t *net, cons
                        uint64_t counter, float *log_alpha, const ctr_sac_alpha_t *alpha_state,
                        float target_entropy, float *loss, float *logp_mean, void *workspace,
                        int64_t workspace_bytes, void *stream);
+
+/* ctr_her_sample_sac: ctr_her_sample with SAC's entropy-regularised target, as ctr_her_sample_td3
+ * is with TD3's.  It writes everything ctr_her_sample writes for the same (her, batch_size, seed,
+ * counter), bit for bit, and in the same launch, for row i of the batch,
+ *     y[0..11]  = ctr_gauss_act's logits of the 12-row policy `actor` on the next_obs row
+ *     eps       = ctr_gauss_act's draw for (seed, counter, row_base 0, row i)       (stream 8)
+ *     t, logp   = ctr_gauss_act's head on y and eps, not deterministic
+ *     q1, q2    = critic1([next_obs row, t]), critic2([next_obs row, t])     (ctr_critic's arithmetic)
+ *     alpha     = (float)exp((double)*log_alpha)
+ *     soft      = fminf(q1, q2) - alpha * logp                  (two f32 roundings, no contraction)
+ *     target    = done != 0 ? reward : (gamma * soft) + reward  (two f32 roundings)
+ * `actor` is the CURRENT policy (SAC has no target policy), critic1 and critic2 the target critics.
+ * The noise key is the sampler's own (seed, counter): next_action and next_logp are the `unit` and
+ * `logp` of the stand-alone ctr_gauss_act(actor, out->next_obs, batch_size, seed, counter, 0, 0,
+ * ...), bit for bit.  A caller who keys the replay draws apart from the collection draws (as
+ * HerReplayBuffer does: its draw seed is not the environments' seed) therefore needs no counter
+ * offsets to keep the two from colliding.  *log_alpha is read on the device when the kernel runs,
+ * never on the host: a captured graph sees the temperature of the replay.
+ * The three blobs take turns in one LDS region beside the sampler's row staging, which is sized for
+ * the largest of them, so every supported policy works with every two supported critics; critic1
+ * and critic2 may be the same struct or blob.  Three launches (the sampler's two scans, then this
+ * kernel); stream-ordered, nothing allocated, nothing read back.
+ * Refused (CTR_EINVAL, before any HIP call, ctr_last_error names ctr_her_sample_sac): whatever
+ * ctr_her_sample refuses (batch_size above 2^31 - 1 among it, so the row index fits the noise key's
+ * 32-bit word); a NULL td, actor, critic1, critic2, log_alpha or target; a shape ctr_gauss_act or
+ * ctr_critic refuses; a NULL or misaligned blob; actor->in_dim != her->obs_dim + 6; a critic's
+ * in_dim != her->obs_dim + 12; a non-finite gamma.  batch_size = 0 is a no-op. */
+typedef struct ctr_her_sac_t {
+    const ctr_actor_t  *actor;      /* the CURRENT policy's 12-row blob (ctr_gauss_pack / _load); scale not read */
+    const ctr_critic_t *critic1;    /* target critics; may be the same struct / blob */
+    const ctr_critic_t *critic2;
+    const float *log_alpha;         /* device, required: read by the kernel, never by the host */
+    float   gamma;                  /* finite */
+    int32_t pad;
+    float  *target;                 /* [B] device, required */
+    float  *q1_next, *q2_next;      /* [B] or NULL */
+    float  *next_action;            /* [B][6] or NULL: t = tanhf(u), what the critics took (ctr_gauss_act's `unit`) */
+    float  *next_logp;              /* [B] or NULL */
+} ctr_her_sac_t;
+int ctr_her_sample_sac(const ctr_her_t *her, int64_t batch_size, uint64_t seed, uint64_t counter,
+                       const ctr_her_batch_t *out, const ctr_her_sac_t *td, void *stream);
 
 /* CtrReachEnv.reset for the environments with mask[i] != 0 (mask NULL = all).
  * goal [n][3] or NULL (sample a goal), system [n] or NULL (sample uniformly).
