@@ -75,9 +75,17 @@ policy's sample on ``next_obs``, the two target critics and the temperature read
 noise is keyed by the replay draw itself, whose seed is not the collection's, so no counter offset is
 needed.
 
+With ``--sac --device-collect`` (``main(..., sac=True, device_collect=True)``; a ValueError without
+``--sac``, whose exploration alone is the policy's own sample) the per-step collection loop becomes one
+call, ``venv.collect_gauss(pi_dev, steps_per_iter, counter=step)``: the policy's stochastic head runs
+inside the fused period kernel, one launch per refill period instead of two per step, with the same
+draws (step ``j`` of the call under ``counter + j``, an env's noise row its global id), so the envs and
+the HER store are what the per-step loop leaves, bit for bit.  With ``--device-targets`` as well an
+iteration is then one launch per refill period on the env side and four calls per update.
+
 usage: python examples/train_ddpg_her.py [--num-envs N] [--iterations I] [--steps-per-iter S]
            [--batch-size B] [--updates-per-iter U] [--hidden 64,64] [--seed 0] [--device cuda]
-           [--device-targets] [--device-polyak] [--device-update] [--td3] [--sac]"""
+           [--device-targets] [--device-polyak] [--device-update] [--td3] [--sac] [--device-collect]"""
 import argparse
 import os
 import sys
@@ -111,12 +119,15 @@ def mlp(n_in, hidden, n_out, tanh):
 
 
 def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, updates_per_iter=40, hidden=(64, 64), seed=0,
-         device="cuda", device_targets=False, device_polyak=False, device_update=False, td3=False, sac=False):
+         device="cuda", device_targets=False, device_polyak=False, device_update=False, td3=False, sac=False,
+         device_collect=False):
     if sac and td3:
         raise ValueError("--sac and --td3 are two algorithms: choose one")
+    if device_collect and not sac:
+        raise ValueError("--device-collect is SAC's collection (venv.collect_gauss): use it with --sac")
     if sac:
         return main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter, hidden, seed, device,
-                        device_targets)
+                        device_targets, device_collect)
     device = torch.device(device)
     device_update = device_update or td3
     device_polyak = device_polyak or device_update
@@ -234,7 +245,7 @@ def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, update
 
 
 def main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter, hidden, seed, device,
-             device_targets=False):
+             device_targets=False, device_collect=False):
     """``main(..., sac=True)``: the same loop with SAC's pieces (the module docstring)."""
     device = torch.device(device)
     torch.manual_seed(seed)
@@ -258,9 +269,13 @@ def main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter,
     losses = []
     step = update = 0
     for it in range(iterations):
-        for _ in range(steps_per_iter):                                      # the policy's sample, the step with its HER feed
-            venv.step(pi_dev.sample(venv.actor_rows(), counter=step, row_base=venv.env_base)["action"])
-            step += 1
+        if device_collect:                                                   # the same steps, one launch per refill period
+            venv.collect_gauss(pi_dev, steps_per_iter, counter=step)
+            step += steps_per_iter
+        else:
+            for _ in range(steps_per_iter):                                  # the policy's sample, the step with its HER feed
+                venv.step(pi_dev.sample(venv.actor_rows(), counter=step, row_base=venv.env_base)["action"])
+                step += 1
         critic_sum = torch.zeros((), device=device)
         policy_sum = torch.zeros((), device=device)
         for _ in range(updates_per_iter):
@@ -309,10 +324,13 @@ if __name__ == "__main__":
                     help="TD3: twin critics, smoothed clipped double-Q targets, delayed policy updates (implies --device-update)")
     ap.add_argument("--sac", action="store_true",
                     help="SAC: a tanh-Gaussian policy, twin critics, the learned temperature (not with --td3)")
+    ap.add_argument("--device-collect", action="store_true",
+                    help="with --sac: the policy's samples inside the fused period kernel (venv.collect_gauss), one "
+                         "launch per refill period instead of two per step")
     args = ap.parse_args()
     out = main(args.num_envs, args.iterations, args.steps_per_iter, args.batch_size, args.updates_per_iter,
                tuple(int(w) for w in args.hidden.split(",")), args.seed, args.device, args.device_targets,
-               args.device_polyak, args.device_update, args.td3, args.sac)
+               args.device_polyak, args.device_update, args.td3, args.sac, args.device_collect)
     for it, (c, p) in enumerate(out["losses"]):
         print("iteration %3d: critic loss %.4g, policy loss %.4g" % (it, c, p))
     if args.sac:

@@ -40,6 +40,8 @@
 //                 thread (ctr_sac_actor_step; ctr_sac.inc)
 //   k_collect     k_rollout with exploration noise on each action and each step recorded into the HER
 //                 store (ctr_collect, at the end of the file)
+//   k_collect_gauss  k_collect whose actions are the tanh-Gaussian policy's samples, k_gauss_act's head
+//                 inside the period loop (ctr_collect_gauss, ctr_sac.inc; the head: ctr_gauss.inc)
 //   k_explore     the exploration noise alone, one env per lane (ctr_explore; explore_lane, ctr_device.hpp)
 //   k_follow      k_rollout without auto-reset in which every env's goal moves along its own waypoint list
 //                 between the steps (ctr_follow, at the end of the file)
@@ -2797,6 +2799,7 @@ int ctr_step_period(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const
 namespace {
 
 #include "ctr_actor.inc"
+#include "ctr_gauss.inc"
 
 __global__ __launch_bounds__(BLOCK) void k_actor(ActorK ak, const float *__restrict__ rows, int64_t n,
                                                  float *__restrict__ actions, float *__restrict__ logits)
@@ -2881,18 +2884,27 @@ __device__ __forceinline__ void follow_retarget(const ctr_follow_t &fw, const ct
     }
 }
 
+// The noise key of k_collect_gauss's launch: the policy's seed and the draw counter of the first step.
+struct GaussKeyK {
+    uint64_t seed, counter;
+};
+
 // k_rollout's body, and with COLLECT k_collect's: each step's action perturbed by the noise (from
 // the clocks the lane carries) and the step recorded into the HER store.  With FOLLOW k_follow's:
 // between two steps the env's goal moves along its waypoints (fw; ctr_follow in the header).  The
 // cursor and the hold count stay in their global rows, read and written between the steps by the
 // env's own lane: no register of theirs lives across the FK, and no wave waits for another.
-template <int MODE, bool COLLECT = false, bool FOLLOW = false>
+// With GAUSS (k_collect_gauss: COLLECT without the noise) ak is the 12-row tanh-Gaussian policy and
+// each step's action is its sample under the key gk, the step's draw counter gk.counter + i.
+template <int MODE, bool COLLECT = false, bool FOLLOW = false, bool GAUSS = false>
 __device__ __forceinline__ void step_body_rollout(const KCfg &kc, const ctr_batch_t &b, const ActorK &ak, int32_t k,
                                                   const ctr_step_out_t &o, int32_t autoreset,
                                                   const ctr_rollout_aux_t &aux, const ExploreK &xk = ExploreK{},
-                                                  const HerK &hk = HerK{}, const ctr_follow_t &fw = ctr_follow_t{})
+                                                  const HerK &hk = HerK{}, const ctr_follow_t &fw = ctr_follow_t{},
+                                                  const GaussKeyK &gk = GaussKeyK{})
 {
     static_assert(!(COLLECT && FOLLOW), "k_follow: no noise and no HER");
+    static_assert(!GAUSS || COLLECT, "k_collect_gauss: the policy's samples are for collection");
     __shared__ SysK s_sys[CTR_MAX_SYSTEMS];
     __shared__ ctr_tube_raw_t s_raw[CTR_MAX_SYSTEMS];
     const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -2936,9 +2948,20 @@ __device__ __forceinline__ void step_body_rollout(const KCfg &kc, const ctr_batc
     period_stage(kc, b, k, autoreset, s_sys, s_raw, stg);
     #pragma unroll 1
     for (int32_t i = 0; i < k; ++i) {
-        float y[6];
-        actor_wave(ak, lds, x, r.a, y);       // every lane of the wave, outside the live region
-        if constexpr (COLLECT) {
+        if constexpr (GAUSS) {
+            // the policy's sample, as k_gauss_act makes it for row_base = env_base (every lane of the
+            // wave, outside the live region; lanes past n: their clamped or zero row, nothing written)
+            float y[12], eps[6], t[6];
+            gauss_logits(ak, lds, x, y);
+            gauss_eps(gk.seed, gk.counter + (uint64_t)i, (uint32_t)(b.env_base + e), eps);
+            gauss_head(y, eps, false, t);
+            #pragma unroll
+            for (int j = 0; j < 6; ++j) r.a[j] = __fmul_rn(ak.scale[j], t[j]);
+        } else {
+            float y[6];
+            actor_wave(ak, lds, x, r.a, y);       // every lane of the wave, outside the live region
+        }
+        if constexpr (COLLECT && !GAUSS) {
             // the noise of (env, reset number, clock before the step): its temporaries die here
             if (xk.on && live) explore_lane(xk.x, xk.scale, (uint64_t)(b.env_base + e), r.ep, r.t, r.a);
         }
@@ -3015,6 +3038,16 @@ __global__ __launch_bounds__(BLOCK) void k_collect(KCfg kc, ctr_batch_t b, Actor
     if constexpr (rollout_mode<MODE>()) step_body_rollout<MODE, true>(kc, b, ak, k, o, autoreset, aux, xk, hk);
 }
 
+// k_collect with the tanh-Gaussian policy's sample as each step's action (ctr_collect_gauss): no
+// ExploreK, the policy's own noise is the exploration.
+template <int MODE>
+__global__ __launch_bounds__(BLOCK) void k_collect_gauss(KCfg kc, ctr_batch_t b, ActorK ak, int32_t k, ctr_step_out_t o,
+                                                         int32_t autoreset, ctr_rollout_aux_t aux, GaussKeyK gk, HerK hk)
+{
+    if constexpr (rollout_mode<MODE>())
+        step_body_rollout<MODE, true, false, true>(kc, b, ak, k, o, autoreset, aux, ExploreK{}, hk, ctr_follow_t{}, gk);
+}
+
 // k_rollout without auto-reset (a compile-time CTR_AUTORESET_OFF: no pool code) whose envs walk
 // their waypoint lists (ctr_follow).
 template <int MODE>
@@ -3025,9 +3058,10 @@ __global__ __launch_bounds__(BLOCK) void k_follow(KCfg kc, ctr_batch_t b, ActorK
         step_body_rollout<MODE, false, true>(kc, b, ak, k, o, CTR_AUTORESET_OFF, aux, ExploreK{}, HerK{}, fw);
 }
 
-// LDS of a workgroup on gfx950, and the static LDS of k_rollout<MODE>, k_collect<MODE> and
-// k_follow<MODE> (the build's resource-usage remarks; k_collect and k_follow add no array
-// of their own): what the blob and the domain tables share the rest with.
+// LDS of a workgroup on gfx950, and the static LDS of k_rollout<MODE>, k_collect<MODE>,
+// k_collect_gauss<MODE> and k_follow<MODE> (the build's resource-usage remarks; k_collect,
+// k_collect_gauss and k_follow add no array of their own): what the blob and the domain tables share
+// the rest with.
 constexpr size_t LDS_PER_WORKGROUP = 160 * 1024;
 constexpr size_t ROLLOUT_STATIC_LDS[6] = {78976, 0, 0, 90240, 78976, 78976};
 
@@ -3048,13 +3082,14 @@ int explore_check(const ctr_explore_t *x, const float *scale, ExploreK *xk)
 }
 
 // ctr_rollout's checks, all before any HIP call (ctr_collect repeats them, with its messages); on
-// success the kernel arguments, and *shm = the launch's dynamic LDS.
+// success the kernel arguments, and *shm = the launch's dynamic LDS.  gauss (ctr_collect_gauss): the
+// actor is the 12-row tanh-Gaussian policy, whose blob has the 6-row actor's size.
 int rollout_check(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *actor, int32_t k,
                   const ctr_step_out_t *out, int32_t autoreset, const ctr_rollout_aux_t *aux, KCfg *kc, ActorK *ak,
-                  ctr_rollout_aux_t *ax, size_t *shm)
+                  ctr_rollout_aux_t *ax, size_t *shm, bool gauss = false)
 {
     if (int r = check_cfg(cfg)) return r;
-    if (int r = actor_check(actor, ak)) return r;
+    if (int r = gauss ? gauss_check(actor, ak) : actor_check(actor, ak)) return r;
     if (ak->in_dim != (cfg->n_systems > 1 ? 14 : 13) + 6)
         return fail(CTR_EINVAL, "ctr_rollout: actor->in_dim must be obs_dim + 6 (19 for one system, 20 for several)");
     // ctr_step_many's eligibility, with its messages (no action table)
@@ -3064,7 +3099,8 @@ int rollout_check(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const c
         return fail(CTR_EINVAL, "ctr_rollout: the episode statistics need CTR_AUTORESET_POOLED (without auto-reset a done "
                                 "environment stays done)");
     if (batch->n == 0) return 0;
-    if (int r = period_refuse_mode1(*kc, "ctr_rollout", "ctr_actor + ctr_step")) return r;
+    if (int r = gauss ? period_refuse_mode1(*kc, "ctr_collect_gauss", "ctr_gauss_act + ctr_step_her")
+                      : period_refuse_mode1(*kc, "ctr_rollout", "ctr_actor + ctr_step")) return r;
     const size_t lane = lane_lds_bytes(*kc), fixed = ROLLOUT_STATIC_LDS[kc->mode < 6 ? kc->mode : 0];
     *shm = lane + ak->bytes + ACTOR_LDS_SLACK;
     if (fixed + *shm > LDS_PER_WORKGROUP) {

@@ -3,10 +3,8 @@
 //
 // ctr_gauss_act: the tanh-Gaussian policy.  ctr_actor's MLP (actor_tile, the bf16 blob) with a 12-row
 // output layer, rows 0..5 the mean and rows 6..11 the log standard deviation; one row per lane, one
-// launch.  The 12 rows sit in the one 32-row output tile: rows 0..3 in acc[0..3] of lane half 0, rows
-// 4..7 in acc[0..3] of lane half 1, rows 8..11 in acc[4..7] of lane half 0 (ctr_actor.inc's
-// register-to-feature formula).  actor_tile adds the bias of rows 0..7; gauss_logits adds that of
-// rows 8..11.
+// launch.  The head's device functions (gauss_layout, gauss_logits, gauss_eps, gauss_head) are in
+// ctr_gauss.inc, ahead of the period kernels, which run them too (k_collect_gauss).
 //
 // ctr_sac_actor_step: the policy's update.  k_sac_grad is k_ddpg_grad<true> with three network
 // images in LDS instead of two (the policy, critic 1, critic 2), the stochastic head between the
@@ -17,81 +15,10 @@
 // ctr_her_sample_sac: the replay draw with SAC's soft target.  k_her_sample_sac is k_her_sample_td3
 // (ctr_critic.inc: td_next_row, td_critic, td_target) with gauss_logits, gauss_eps and gauss_head
 // in the target policy's place.
+//
+// ctr_collect_gauss: the entry point of k_collect_gauss (ctr_kernels.hip), ctr_collect with the policy's
+// sample in the actor's and the noise's place.
 namespace {
-
-int gauss_layout(const ctr_actor_t *a, ActorK *ak)
-{
-    if (!a) return fail(CTR_EINVAL, "actor is NULL");
-    return mlp_layout(MlpShape{"actor", 6, 12, a->in_dim, a->n_hidden, a->width}, ak);
-}
-
-// Six standard normals of row i of draw (seed, counter): two Philox blocks of stream 8, the
-// uniforms and Box-Muller as td3_smooth makes them (ctr_critic.inc), spelled out in the same way.
-__device__ __forceinline__ void gauss_eps(uint64_t seed, uint64_t counter, uint32_t i, float z[6])
-{
-#pragma clang fp contract(off)
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const uint32_t c1 = (uint32_t)counter, c3 = (uint32_t)(counter >> 32) ^ (8u << 24);
-    uint32_t w0[4] = {0u, c1, i, c3}, w1[4] = {1u, c1, i, c3};
-    philox(w0, k0, k1);
-    philox(w1, k0, k1);
-    const float u[6] = {(float)(w0[0] >> 8) * 0x1p-24f, (float)(w0[1] >> 8) * 0x1p-24f, (float)(w0[2] >> 8) * 0x1p-24f,
-                        (float)(w0[3] >> 8) * 0x1p-24f, (float)(w1[0] >> 8) * 0x1p-24f, (float)(w1[1] >> 8) * 0x1p-24f};
-    #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const float r = sqrtf(__fmul_rn(-2.f, logf(__fsub_rn(1.f, u[2 * j]))));
-        float sn, cs;
-        sincosf(__fmul_rn(6.2831855f, u[2 * j + 1]), &sn, &cs);
-        z[2 * j] = __fmul_rn(r, cs);
-        z[2 * j + 1] = __fmul_rn(r, sn);
-    }
-}
-
-// max(x, 0) + log1p(exp(-|x|)): finite for every finite x
-__device__ __forceinline__ float gauss_softplus(float x)
-{
-#pragma clang fp contract(off)
-    return __fadd_rn(fmaxf(x, 0.f), log1pf(expf(-fabsf(x))));
-}
-
-// The head on one row's 12 outputs: t[i] = tanh(u_i), returns logp (the header's formulas, term by
-// term, summed over i = 0..5 in that order).  det: u = the mean, eps = 0.
-__device__ __forceinline__ float gauss_head(const float y[12], const float eps[6], bool det, float t[6])
-{
-#pragma clang fp contract(off)
-    float lp = 0.f;
-    #pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const float s = fminf(fmaxf(y[6 + i], -20.f), 2.f);
-        const float u = det ? y[i] : fmaf(expf(s), eps[i], y[i]);
-        t[i] = tanhf(u);
-        const float a = __fsub_rn(__fsub_rn(__fmul_rn(-0.5f, __fmul_rn(eps[i], eps[i])), s), 0.9189385f);
-        const float c = __fmul_rn(2.f, __fsub_rn(__fsub_rn(0.6931472f, u), gauss_softplus(__fmul_rn(-2.f, u))));
-        lp = __fadd_rn(lp, __fsub_rn(a, c));
-    }
-    return lp;
-}
-
-// actor_logits for the 12-row head: the lane's row's 12 outputs, biases added.
-__device__ __forceinline__ void gauss_logits(const ActorK &ak, const char *lds, const float x[20], float y[12])
-{
-    const int lane = (int)(threadIdx.x & 63), h = lane >> 5, r = lane & 31;
-    const int lo = ak.n_hidden;                   // 1..3: the offset by constant index
-    const uint32_t bo = lo == 1 ? ak.b_off[1] : (lo == 2 ? ak.b_off[2] : ak.b_off[3]);
-    const float4 bb = *reinterpret_cast<const float4 *>(lds + bo + 32);      // the bias of rows 8..11
-    #pragma unroll
-    for (int i = 0; i < 12; ++i) y[i] = 0.f;
-    #pragma unroll 1
-    for (int c = 0; c < 2; ++c) {
-        const actor_f32x16 acc = actor_tile<20>(ak, lds, x, c);
-        const float hi[4] = {acc[4] + bb.x, acc[5] + bb.y, acc[6] + bb.z, acc[7] + bb.w};
-        #pragma unroll
-        for (int i = 0; i < 12; ++i) {
-            const float v = __shfl(i < 8 ? acc[i & 3] : hi[i & 3], i >= 4 && i < 8 ? 32 + r : r);
-            y[i] = h == c ? v : y[i];
-        }
-    }
-}
 
 struct GaussK {
     uint64_t seed, counter, row_base;
@@ -449,6 +376,35 @@ int ctr_her_sample_sac(const ctr_her_t *her, int64_t batch_size, uint64_t seed, 
     hipLaunchKernelGGL(k_her_sample_sac, dim3(grid_for(batch_size)), dim3(BLOCK), shm, (hipStream_t)stream, HerK{*her},
                        batch_size, seed, counter, *out, ak, ck1, ck2, tk);
     return hip_check("ctr_her_sample_sac launch");
+}
+
+int ctr_collect_gauss(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *policy, uint64_t seed,
+                      uint64_t counter, const ctr_her_t *her, int32_t k, const ctr_step_out_t *out, int32_t autoreset,
+                      const ctr_rollout_aux_t *aux, void *stream)
+{
+    const char *fn = "ctr_collect_gauss";
+    KCfg kc;
+    ActorK ak;
+    ctr_rollout_aux_t ax;
+    size_t shm = 0;
+    // ctr_rollout's checks on the 12-row policy, then ctr_collect's of the store, under this name
+    if (int r = td_named(fn, rollout_check(cfg, batch, policy, k, out, autoreset, aux, &kc, &ak, &ax, &shm, true))) return r;
+    if (int r = td_named(fn, check_her(her, "ctr_step_her: her is NULL"))) return r;
+    if (batch->n != her->n) return ddpg_fail(fn, "batch and store sizes differ");
+    if (batch->env_base != her->env_base) return ddpg_fail(fn, "batch and store env_base differ");
+    if (her->t_max != cfg->max_steps)
+        return ddpg_fail(fn, "her->t_max must equal cfg->max_steps (episodes close at the time limit)");
+    // the global env id is the noise key's 32-bit row word, as ctr_gauss_act's row_base + row
+    if (batch->env_base < 0 || batch->env_base > 0x100000000ll - batch->n)
+        return ddpg_fail(fn, "batch->env_base + n must stay within 0..2^32");
+    const ctr_batch_t b = *batch;
+    const ctr_step_out_t o = *out;
+    if (b.n == 0) return 0;
+    const GaussKeyK gk = {seed, counter};
+    const HerK hk = {*her};
+    CTR_LAUNCH_PERIOD(k_collect_gauss, kc.mode, , dim3(grid_for(b.n)), shm, (hipStream_t)stream, kc, b, ak, k, o,
+                      autoreset, ax, gk, hk);
+    return hip_check("ctr_collect_gauss launch");
 }
 
 int64_t ctr_sac_workspace_bytes(const ctr_actor_t *actor, const ctr_critic_t *critic1, const ctr_critic_t *critic2,

@@ -1,10 +1,11 @@
 """ctypes mirrors of ctr_sac_alpha_t and ctr_her_sac_t and the prototypes of ctr_gauss_blob_bytes,
-ctr_gauss_pack, ctr_gauss_load, ctr_gauss_act, ctr_sac_workspace_bytes, ctr_sac_actor_step and
-ctr_her_sample_sac (include/ctr_reach_amd.h, "SAC": added within ABI 17).  ``_abi.load`` binds them;
-tests/test_host_sac.py and tests/test_host_sac_target.py check the mirrors against the header."""
+ctr_gauss_pack, ctr_gauss_load, ctr_gauss_act, ctr_sac_workspace_bytes, ctr_sac_actor_step,
+ctr_her_sample_sac and ctr_collect_gauss (include/ctr_reach_amd.h, "SAC" and next to ctr_collect: added
+within ABI 17).  ``_abi.load`` binds them; tests/test_host_sac.py, tests/test_host_sac_target.py and
+tests/test_host_collect_gauss.py check the mirrors against the header."""
 import ctypes
 
-from ._abi import CtrActor, CtrHer, CtrHerBatch, _P
+from ._abi import CtrActor, CtrBatch, CtrEnvConfig, CtrHer, CtrHerBatch, CtrRolloutAux, CtrStepOut, _P
 from ._abi_critic import CtrCritic
 from ._abi_ddpg import CtrDdpgAdam, CtrDdpgNet
 from ._abi_td3 import CriticPair
@@ -43,3 +44,7 @@ def bind(L):
     if hasattr(L, "ctr_her_sample_sac"):           # (a build from before the symbol lacks it)
         L.ctr_her_sample_sac.argtypes = [ctypes.POINTER(CtrHer), i64, u64, u64, ctypes.POINTER(CtrHerBatch),
                                          ctypes.POINTER(CtrHerSac), _P]
+    if hasattr(L, "ctr_collect_gauss"):            # (a build from before the symbol lacks it)
+        L.ctr_collect_gauss.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch), A, u64, u64,
+                                        ctypes.POINTER(CtrHer), i32, ctypes.POINTER(CtrStepOut), i32,
+                                        ctypes.POINTER(CtrRolloutAux), _P]

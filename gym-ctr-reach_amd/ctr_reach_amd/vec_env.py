@@ -801,6 +801,35 @@ class CtrReachVecEnv(object):
             self.lib.ctr_collect(self.cfg, self._batch, actor._struct, noise._struct if noise is not None else None,
                                  self._her._h, k, self._out, mode, aux, sp), "ctr_collect"))
 
+    def collect_gauss(self, policy, steps, counter, record_actions=False, stream=None):
+        """collect() for SAC: every step's action is the sample of ``policy`` (policy.GaussianActor,
+        keyed by its ``seed``) on the env's current row, and every transition is recorded into the
+        HER store bound by enable_her(), each refill period's steps as one launch
+        (ctr_collect_gauss: the stochastic head runs inside the fused period kernel).  Step ``j`` of
+        the call draws under ``counter + j``, across the launches the call splits into at refill
+        boundaries, and an env's noise row is its global id: the state, the outputs, the HER store,
+        the statistics and the host bookkeeping afterwards are those of ``steps`` rounds of
+        ``step_raw(policy.sample(actor_rows(), counter=counter + j, row_base=env_base)["action"])``,
+        bit for bit.  A training loop passes its running step count and adds ``steps`` to it.
+        TypeError for a policy that is not a GaussianActor; RuntimeError wherever collect() raises it
+        (collect_ineligible).  There is no deterministic variant: ``collect(policy.mean_actor(),
+        steps)`` is it.  Returns the applied actions [steps, N, 6] with ``record_actions``."""
+        from .policy import GaussianActor
+        if not isinstance(policy, GaussianActor):
+            raise TypeError("collect_gauss: the policy must be a GaussianActor")
+        why = self.collect_ineligible()
+        if why:
+            raise RuntimeError("collect_gauss: " + why)
+        done = [int(counter)]                  # the draw of the next launch's first step
+
+        def call(k, mode, aux, sp):
+            _abi.check(self.lib.ctr_collect_gauss(self.cfg, self._batch, policy._struct, policy.seed,
+                                                  done[0] & 0xFFFFFFFFFFFFFFFF, self._her._h, k, self._out, mode, aux,
+                                                  sp), "ctr_collect_gauss")
+            done[0] += k
+
+        return self._closed_loop("collect_gauss", policy, steps, record_actions, stream, call)
+
     def capture_steps(self, actions, stream=None):
         """Capture len(actions) consecutive steps (step_raw, with the pool refills that fall due)
         into one HIP graph; ``StepGraph.replay()`` then runs them with a single launch, so a

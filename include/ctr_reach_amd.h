@@ -52,7 +52,8 @@
  *                       for a continuous action space, SAC (Haarnoja et al. 2018), with its defaults:
  *                       the tanh-Gaussian policy's sample and log-probability, the policy's update
  *                       under the smaller of two critics with the learned temperature, and the
- *                       entropy-regularised target together with the replay draw that feeds it
+ *                       entropy-regularised target together with the replay draw that feeds it;
+ *                       ctr_collect_gauss: ctr_collect with that policy's samples as the actions
  *   ctr_explore / ctr_collect
  *                       the data collection of the reference's training pipeline, stable-baselines
  *                       DDPG under HER: NormalActionNoise clipped to the action box and
@@ -633,6 +634,36 @@ int ctr_explore(const ctr_batch_t *batch, const ctr_explore_t *explore, const fl
 int ctr_collect(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *actor,
                 const ctr_explore_t *explore, const ctr_her_t *her, int32_t k, const ctr_step_out_t *out,
                 int32_t autoreset, const ctr_rollout_aux_t *aux, void *stream);
+
+/* ctr_collect for SAC (a symbol added within ABI 17: no existing entry point or struct changes):
+ * every step's action is the tanh-Gaussian policy's own sample ("SAC" below: ctr_gauss_act), and
+ * there is no ctr_explore_t, the policy's noise being the exploration.  `policy` is the 12-row blob
+ * of ctr_gauss_pack / ctr_gauss_load with its action box in scale; seed is the noise key and counter
+ * the draw of the call's first step.  Afterwards the batch, the outputs, the pool, the refill queue,
+ * every buffer of the HER store, aux->actions (the applied actions) and the statistics are exactly
+ * what k rounds i = 0..k-1 of
+ *     ctr_gauss_act(policy, row, n, seed, counter + i, batch->env_base, 0, actions, NULL, NULL, NULL, ...);
+ *     ctr_step_her(cfg, batch, actions, out, autoreset, her, ...)
+ * with `row` the environments' flat rows [observation, achieved_goal, desired_goal] before the step
+ * and batch->work_parity toggled after every step would have left, bit for bit.  counter + i is a
+ * 64-bit sum (modulo 2^64) whose low and high halves are the noise counter's words, and the row word
+ * is the global env id batch->env_base + e: an env's action in a step is a pure function of its
+ * row, the weights and (seed, counter + i, global env id), not of the launch, the lane, the shard
+ * or of how the steps are cut into calls.  One launch; nothing is read back or allocated, so it can
+ * be captured into a graph.  There is no deterministic flag: ctr_collect with explore = NULL and
+ * the 6-row actor built from the head's first six rows already is the deterministic policy, bit for
+ * bit.
+ * Refused (CTR_EINVAL, before any HIP call, ctr_last_error names ctr_collect_gauss): wherever
+ * ctr_rollout is, with the policy's shape judged as ctr_gauss_act judges it (the blob has the 6-row
+ * actor's size, so the LDS budget and its message are ctr_rollout's; the compliant model's scipy
+ * RK45 with a y pre-curvature, whose kernel would spill to scratch, is refused by name: use
+ * ctr_gauss_act + ctr_step_her there); where ctr_step_her is (a NULL or malformed store,
+ * her->t_max != cfg->max_steps, her->n or her->env_base different from the batch's);
+ * batch->env_base < 0 or batch->env_base + n above 2^32 (the env id is the key's 32-bit row word,
+ * as ctr_gauss_act's row_base + row).  n = 0 is a no-op. */
+int ctr_collect_gauss(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_actor_t *policy,
+                      uint64_t seed, uint64_t counter, const ctr_her_t *her, int32_t k,
+                      const ctr_step_out_t *out, int32_t autoreset, const ctr_rollout_aux_t *aux, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Retargeting and waypoint following (entry points added within ABI 17: no existing entry point or

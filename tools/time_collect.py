@@ -7,7 +7,13 @@ back-to-back periods, each with its refill, best of 3), every line in a fresh pr
   (b) collect, HER                    the actor and the HER recording in one launch per period
   (b) collect, HER + noise            ... with the exploration noise (sigma 0.3, random_eps 0.3)
   (c) act + explore + step_raw, HER   the same, eager: ctr_actor, ctr_explore, ctr_step_her per step
-usage: python tools/time_collect.py [--envs N] [--parent-lib PATH] [--spread K] [--json PATH]
+With --gauss, SAC's collection instead (a GaussianActor [64, 64] with the same hidden layers' seed),
+--spread fresh processes of every line, the two builds interleaved:
+  (d) collect_gauss                   the policy's sample and the HER recording in one launch per period
+  (e) sample + step_raw, HER          the same, eager: torch.cat of the rows, ctr_gauss_act, ctr_step_her per
+                                      step; on --parent-lib (the yardstick of (d)) and on this build's
+  (a), (b) collect, HER               on both builds: did k_rollout and k_collect keep their times
+usage: python tools/time_collect.py [--envs N] [--parent-lib PATH] [--spread K] [--json PATH] [--gauss]
        python tools/time_collect.py --case NAME      (one line, in this process; what the above starts)"""
 import argparse
 import json
@@ -19,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gym-ctr-reach_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-CASES = ("rollout", "collect_her", "collect_her_noise", "eager_her_noise")
+CASES = ("rollout", "collect_her", "collect_her_noise", "eager_her_noise", "collect_gauss", "eager_gauss")
 HIDDEN = (64, 64)
 
 
@@ -41,6 +47,27 @@ def run_case(name, n):
         return env
 
     env = make_env(n) if name == "rollout" else make_her_env()
+    if name in ("collect_gauss", "eager_gauss"):
+        from ctr_reach_amd.policy import GaussianActor
+        seq = make_seq(HIDDEN, env.obs_dim + 6)[:-2]          # the hidden layers; a 12-row head, no Tanh
+        torch.manual_seed(3)
+        seq.append(torch.nn.Linear(HIDDEN[-1], 12).to("cuda:0"))
+        pi = GaussianActor.from_torch(seq, env.action_space.high, "cuda:0", seed=1)
+        step = [0]                                            # the running draw counter
+
+        def fused():
+            env.collect_gauss(pi, R, counter=step[0])
+            step[0] += R
+
+        def eager():
+            for _ in range(R):
+                env.step_raw(pi.sample(env.actor_rows(), counter=step[0], row_base=env.env_base)["action"])
+                step[0] += 1
+
+        res = timed(fused if name == "collect_gauss" else eager)
+        res.update(case=name, envs=n, device=torch.cuda.get_device_name(0),
+                   lib="--parent-lib" if os.environ.get("CTR_REACH_AMD_LIB") else "this build")
+        return res
     actor = MlpActor.from_torch(make_seq(HIDDEN, env.obs_dim + 6), env.action_space.high, "cuda:0")
     if name == "rollout":
         res = timed(lambda: env.rollout(actor, R))
@@ -79,6 +106,7 @@ def main():
     ap.add_argument("--parent-lib", default=None, help="an older build of libctr_reach_amd.so, for (a)")
     ap.add_argument("--spread", type=int, default=3, help="fresh-process runs of (a) per library")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--gauss", action="store_true", help="SAC's collection: (d), (e) and (a), (b) on both builds")
     args = ap.parse_args()
     if args.case:
         print(json.dumps(run_case(args.case, args.envs)))
@@ -95,9 +123,17 @@ def main():
         if args.parent_lib:
             line("(a) rollout, parent build, run %d" % k, "rollout", os.path.abspath(args.parent_lib))
         line("(a) rollout, this build, run %d" % k, "rollout")
-    line("(b) collect, HER", "collect_her")
-    line("(b) collect, HER + noise", "collect_her_noise")
-    line("(c) act + explore + step_raw, fused HER", "eager_her_noise")
+        if not args.gauss:
+            continue
+        for label, name in (("(b) collect, HER", "collect_her"), ("(e) sample + step_raw, fused HER", "eager_gauss")):
+            if args.parent_lib:
+                line("%s, parent build, run %d" % (label, k), name, os.path.abspath(args.parent_lib))
+            line("%s, this build, run %d" % (label, k), name)
+        line("(d) collect_gauss, this build, run %d" % k, "collect_gauss")
+    if not args.gauss:
+        line("(b) collect, HER", "collect_her")
+        line("(b) collect, HER + noise", "collect_her_noise")
+        line("(c) act + explore + step_raw, fused HER", "eager_her_noise")
     if args.json:
         with open(args.json, "w") as f:
             json.dump({"lines": lines}, f, indent=1)
