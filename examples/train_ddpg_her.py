@@ -83,9 +83,17 @@ draws (step ``j`` of the call under ``counter + j``, an env's noise row its glob
 the HER store are what the per-step loop leaves, bit for bit.  With ``--device-targets`` as well an
 iteration is then one launch per refill period on the env side and four calls per update.
 
+With ``--sac --update-call`` (``main(..., sac=True, update_call=True)``; a ValueError without ``--sac``; it
+implies ``--device-targets``) the iteration's whole inner loop is one call,
+``learner.update(her, pi_dev, [(targets_dev[0], targets[0]), (targets_dev[1], targets[1])], batch_size, GAMMA,
+SAC_TAU, updates=updates_per_iter, history=hist)`` (ctr_sac_update): the same updates bit for bit, five
+launches each instead of nine, the sampler's scans once per iteration, and no host work between the
+updates.  The iteration's losses come from ``hist`` ([updates, 5]: the two critic losses, the policy's
+loss, logp_mean, log_alpha per update) in the iteration's one host read.
+
 usage: python examples/train_ddpg_her.py [--num-envs N] [--iterations I] [--steps-per-iter S]
            [--batch-size B] [--updates-per-iter U] [--hidden 64,64] [--seed 0] [--device cuda]
-           [--device-targets] [--device-polyak] [--device-update] [--td3] [--sac] [--device-collect]"""
+           [--device-targets] [--device-polyak] [--device-update] [--td3] [--sac] [--device-collect] [--update-call]"""
 import argparse
 import os
 import sys
@@ -120,14 +128,16 @@ def mlp(n_in, hidden, n_out, tanh):
 
 def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, updates_per_iter=40, hidden=(64, 64), seed=0,
          device="cuda", device_targets=False, device_polyak=False, device_update=False, td3=False, sac=False,
-         device_collect=False):
+         device_collect=False, update_call=False):
     if sac and td3:
         raise ValueError("--sac and --td3 are two algorithms: choose one")
     if device_collect and not sac:
         raise ValueError("--device-collect is SAC's collection (venv.collect_gauss): use it with --sac")
+    if update_call and not sac:
+        raise ValueError("--update-call is SAC's update (SacLearner.update): use it with --sac")
     if sac:
         return main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter, hidden, seed, device,
-                        device_targets, device_collect)
+                        device_targets or update_call, device_collect, update_call)
     device = torch.device(device)
     device_update = device_update or td3
     device_polyak = device_polyak or device_update
@@ -245,7 +255,7 @@ def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, update
 
 
 def main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter, hidden, seed, device,
-             device_targets=False, device_collect=False):
+             device_targets=False, device_collect=False, update_call=False):
     """``main(..., sac=True)``: the same loop with SAC's pieces (the module docstring)."""
     device = torch.device(device)
     torch.manual_seed(seed)
@@ -268,6 +278,7 @@ def main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter,
     targets_dev = [MlpCritic.from_torch(targ, device) for targ in targets]
     losses = []
     step = update = 0
+    hist = torch.zeros((updates_per_iter, 5), dtype=torch.float32, device=device) if update_call else None
     for it in range(iterations):
         if device_collect:                                                   # the same steps, one launch per refill period
             venv.collect_gauss(pi_dev, steps_per_iter, counter=step)
@@ -276,6 +287,12 @@ def main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter,
             for _ in range(steps_per_iter):                                  # the policy's sample, the step with its HER feed
                 venv.step(pi_dev.sample(venv.actor_rows(), counter=step, row_base=venv.env_base)["action"])
                 step += 1
+        if update_call:                                                      # the iteration's updates: one call
+            learner.update(her, pi_dev, list(zip(targets_dev, targets)), batch_size, GAMMA, SAC_TAU,
+                           updates=updates_per_iter, history=hist)
+            h = hist.sum(0).tolist()                                         # the iteration's only host read
+            losses.append((0.5 * (h[0] + h[1]) / max(updates_per_iter, 1), h[2] / max(updates_per_iter, 1)))
+            continue
         critic_sum = torch.zeros((), device=device)
         policy_sum = torch.zeros((), device=device)
         for _ in range(updates_per_iter):
@@ -327,10 +344,12 @@ if __name__ == "__main__":
     ap.add_argument("--device-collect", action="store_true",
                     help="with --sac: the policy's samples inside the fused period kernel (venv.collect_gauss), one "
                          "launch per refill period instead of two per step")
+    ap.add_argument("--update-call", action="store_true",
+                    help="with --sac: an iteration's updates from one learner.update call (implies --device-targets)")
     args = ap.parse_args()
     out = main(args.num_envs, args.iterations, args.steps_per_iter, args.batch_size, args.updates_per_iter,
                tuple(int(w) for w in args.hidden.split(",")), args.seed, args.device, args.device_targets,
-               args.device_polyak, args.device_update, args.td3, args.sac, args.device_collect)
+               args.device_polyak, args.device_update, args.td3, args.sac, args.device_collect, args.update_call)
     for it, (c, p) in enumerate(out["losses"]):
         print("iteration %3d: critic loss %.4g, policy loss %.4g" % (it, c, p))
     if args.sac:

@@ -1,8 +1,9 @@
-"""ctypes mirrors of ctr_sac_alpha_t and ctr_her_sac_t and the prototypes of ctr_gauss_blob_bytes,
-ctr_gauss_pack, ctr_gauss_load, ctr_gauss_act, ctr_sac_workspace_bytes, ctr_sac_actor_step,
-ctr_her_sample_sac and ctr_collect_gauss (include/ctr_reach_amd.h, "SAC" and next to ctr_collect: added
-within ABI 17).  ``_abi.load`` binds them; tests/test_host_sac.py, tests/test_host_sac_target.py and
-tests/test_host_collect_gauss.py check the mirrors against the header."""
+"""ctypes mirrors of ctr_sac_alpha_t, ctr_her_sac_t and ctr_sac_update_t and the prototypes of
+ctr_gauss_blob_bytes, ctr_gauss_pack, ctr_gauss_load, ctr_gauss_act, ctr_sac_workspace_bytes,
+ctr_sac_actor_step, ctr_her_sample_sac, ctr_collect_gauss and ctr_sac_update (include/ctr_reach_amd.h,
+"SAC" and next to ctr_collect: added within ABI 17).  ``_abi.load`` binds them; tests/test_host_sac.py,
+tests/test_host_sac_target.py, tests/test_host_collect_gauss.py and tests/test_host_sac_update.py check
+the mirrors against the header."""
 import ctypes
 
 from ._abi import CtrActor, CtrBatch, CtrEnvConfig, CtrHer, CtrHerBatch, CtrRolloutAux, CtrStepOut, _P
@@ -28,6 +29,21 @@ class CtrHerSac(ctypes.Structure):
 LayersPair = ctypes.POINTER(_P) * 2                # const float *const *const critic_W[2]
 
 
+class CtrSacUpdate(ctypes.Structure):
+    """ctr_sac_update_t: everything a run of SAC updates takes (ctr_sac_update), once."""
+    _fields_ = [("her", ctypes.POINTER(CtrHer)), ("batch_size", ctypes.c_int64), ("draw_seed", ctypes.c_uint64),
+                ("draw_counter", ctypes.c_uint64), ("batch", ctypes.POINTER(CtrHerBatch)), ("target", _P), ("q1_next", _P),
+                ("q2_next", _P), ("next_action", _P), ("next_logp", _P), ("gamma", ctypes.c_float), ("tau", ctypes.c_float),
+                ("policy", ctypes.POINTER(CtrActor)), ("policy_net", ctypes.POINTER(CtrDdpgNet)),
+                ("policy_adam", ctypes.POINTER(CtrDdpgAdam)), ("critic", ctypes.POINTER(CtrCritic) * 2),
+                ("critic_net", ctypes.POINTER(CtrDdpgNet) * 2), ("critic_adam", ctypes.POINTER(CtrDdpgAdam)), ("scale", _P),
+                ("critic_targ", ctypes.POINTER(CtrCritic) * 2), ("W_targ", ctypes.POINTER(_P) * 2),
+                ("b_targ", ctypes.POINTER(_P) * 2), ("seed", ctypes.c_uint64), ("step_counter", ctypes.c_uint64),
+                ("log_alpha", _P), ("alpha", ctypes.POINTER(CtrSacAlpha)), ("target_entropy", ctypes.c_float),
+                ("pad", ctypes.c_int32), ("critic_loss", _P), ("actor_loss", _P), ("logp_mean", _P), ("workspace", _P),
+                ("workspace_bytes", ctypes.c_int64), ("history", _P)]
+
+
 def bind(L):
     i64, u64, i32 = ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32
     A = ctypes.POINTER(CtrActor)
@@ -48,3 +64,5 @@ def bind(L):
         L.ctr_collect_gauss.argtypes = [ctypes.POINTER(CtrEnvConfig), ctypes.POINTER(CtrBatch), A, u64, u64,
                                         ctypes.POINTER(CtrHer), i32, ctypes.POINTER(CtrStepOut), i32,
                                         ctypes.POINTER(CtrRolloutAux), _P]
+    if hasattr(L, "ctr_sac_update"):               # (a build from before the symbol lacks it)
+        L.ctr_sac_update.argtypes = [ctypes.POINTER(CtrSacUpdate), i32, _P]

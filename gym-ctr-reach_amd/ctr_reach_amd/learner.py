@@ -489,6 +489,152 @@ class SacLearner(object):
         if rc:
             _abi.check(rc, "ctr_sac_actor_step")
 
+    def _update_check(self, her, pi, targets, batch_size, gamma, tau, updates, history):
+        """``update``'s checks (``sample_sac``'s, ``critic_step``'s, ``load_``'s and ``polyak_``'s), before
+        anything is allocated, converted or written -> (B, updates, gamma, tau, [(net, target layers), ...])."""
+        import torch
+        from .policy import GaussianActor, MlpCritic
+        dev = self.device
+
+        def elsewhere(d):
+            return d.type != dev.type or (None not in (d.index, dev.index) and d.index != dev.index)
+
+        hdev = her.venv.device
+        if elsewhere(hdev):
+            raise ValueError("update: the buffer is on %s, the learner on %s" % (hdev, dev))
+        if not isinstance(pi, GaussianActor):
+            raise ValueError("update: pi must be a GaussianActor (the 12-row head), not %s" % type(pi).__name__)
+        targets = [tuple(t) for t in targets]
+        if len(targets) != 2 or any(len(t) != 2 for t in targets):
+            raise ValueError("update: targets is [(critic1_targ_dev, critic1_targ), (critic2_targ_dev, critic2_targ)]")
+        for m, (net, _) in enumerate(targets):
+            if not isinstance(net, MlpCritic):
+                raise ValueError("update: target %d must be an MlpCritic, not %s" % (m + 1, type(net).__name__))
+        for net, name in ((pi, "policy"), (targets[0][0], "target 1"), (targets[1][0], "target 2")):
+            if getattr(net, "blob", None) is None:
+                raise ValueError("update: the %s must be on the device" % name)
+            if elsewhere(net.device):
+                raise ValueError("update: the %s is on %s, the learner on %s" % (name, net.device, dev))
+        if targets[0][0] is targets[1][0]:
+            raise ValueError("update: the two targets are one MlpCritic: each has its own blob")
+        gamma, tau = float(gamma), float(tau)
+        if not np.isfinite(gamma):
+            raise ValueError("update: gamma must be finite")
+        if not 0.0 <= tau <= 1.0:
+            raise ValueError("update: tau must be in [0, 1]")
+        B, updates = int(batch_size), int(updates)
+        if not 0 <= B <= self.max_batch:
+            raise ValueError("update: batch_size = %d, the learner was built for max_batch = %d" % (B, self.max_batch))
+        if updates < 0:
+            raise ValueError("update: updates must be >= 0")
+        if her.obs_dim + 6 != self.in_dim:
+            raise ValueError("update: the buffer's rows are %d floats, the policy's %d" % (her.obs_dim + 6, self.in_dim))
+        pi._device_layers(self._actor.params, "update: the policy's ")            # load_'s: pi has the masters' shape
+        done = []
+        for m, (net, target) in enumerate(targets):
+            net._device_layers(self._critics[m].params, "update: target %d: online " % (m + 1))
+            tg = net._device_layers(target, "update: target %d: target " % (m + 1), target=True)
+            done.append((net, tg))
+        if history is not None:
+            if not (isinstance(history, torch.Tensor) and history.dtype == torch.float32 and not elsewhere(history.device)
+                    and tuple(history.shape) == (updates, 5) and history.is_contiguous()):
+                raise ValueError("update: history must be a contiguous float32 [updates, 5] = [%d, 5] tensor on %s"
+                                 % (updates, dev))
+        return B, updates, gamma, tau, done
+
+    def update(self, her, pi, targets, batch_size, gamma, tau, updates=1, history=None, return_next=False, stream=None):
+        """``updates`` whole SAC updates from one call (ctr_sac_update): each is what
+
+            batch = her.sample_sac(batch_size, pi, critic1_targ_dev, critic2_targ_dev, gamma, learner.log_alpha)
+            learner.critic_step(batch["obs"], batch["action"], batch["target"])
+            learner.actor_step(batch["obs"])
+            pi.load_(policy)
+            polyak_([(critic1_targ_dev, critic1, critic1_targ), (critic2_targ_dev, critic2, critic2_targ)], tau)
+
+        leaves, bit for bit, in five launches instead of nine and without the host work of five calls;
+        the sampler's two scans run once per call.  ``her``: the ``HerReplayBuffer``; ``pi``: the
+        ``GaussianActor`` whose blob is refreshed from the learner's own policy masters; ``targets``:
+        [(critic1_targ_dev, critic1_targ), (critic2_targ_dev, critic2_targ)], each the target's
+        ``MlpCritic`` and the owner of its float32 parameters (``nn.Sequential`` or [(W, b), ...]) as
+        ``polyak_`` takes them.  The draws run under the buffer's draw seed and counter, the policy's
+        noise under the learner's seed and counter, as the five calls' would.
+
+        Returns ``sample_sac``'s dict (with ``return_next`` also q1_next, q2_next, next_action,
+        next_logp), holding the LAST update's draw.  Its tensors are allocated on the first call for a
+        ``batch_size`` and reused: THE NEXT ``update`` CALL OVERWRITES THEM.  ``history``: None, or a
+        contiguous float32 [updates, 5] tensor on the device; row i gets update i's critic 1 loss,
+        critic 2 loss, actor loss, logp_mean and log_alpha after its step, and the dict returns it under
+        "history".  ``critic_loss``, ``actor_loss`` and ``logp_mean`` hold the last update's values.
+
+        Every check of the five calls is made first (ValueError, nothing converted, nothing written).
+        Afterwards ``her``'s draw counter and the learner's ``counter`` have advanced by ``updates``,
+        ``pi`` and the target nets are as ``load_`` / ``polyak_`` leave them (sources set, host copies
+        dropped) and the buffer keeps ``log_alpha`` referenced as ``sample_sac`` does.  Asynchronous:
+        no allocation after the first call, no host read; a captured call repeats its draws on replay
+        (the counters are arguments).  The call's struct is built once per (her, pi, targets,
+        batch_size) and cached."""
+        import torch
+        from . import _abi_sac
+        B, updates, gamma, tau, done = self._update_check(her, pi, targets, batch_size, gamma, tau, updates, history)
+        key = (id(her), id(pi), B, bool(return_next), pi.blob.data_ptr()) + tuple(
+            (id(net), net.blob.data_ptr()) + tuple(t.data_ptr() for pair in tg for t in pair) for net, tg in done)
+        cache = self.__dict__.setdefault("_update_cache", {})
+        entry = cache.get(key)
+        if entry is None:
+            if len(cache) >= 8:
+                cache.clear()
+            _, out, hb = her._batch(B, False)
+            dev = self.device
+            out["target"] = torch.empty(B, dtype=torch.float32, device=dev)
+            if return_next:
+                out["q1_next"] = torch.empty(B, dtype=torch.float32, device=dev)
+                out["q2_next"] = torch.empty(B, dtype=torch.float32, device=dev)
+                out["next_action"] = torch.empty((B, 6), dtype=torch.float32, device=dev)
+                out["next_logp"] = torch.empty(B, dtype=torch.float32, device=dev)
+            u = _abi_sac.CtrSacUpdate()
+            u.her, u.batch_size, u.draw_seed, u.batch = ctypes.pointer(her._h), B, her._draw_seed(None), ctypes.pointer(hb)
+            u.target, u.q1_next, u.q2_next = _abi.ptr(out["target"]), _abi.ptr(out.get("q1_next")), _abi.ptr(out.get("q2_next"))
+            u.next_action, u.next_logp = _abi.ptr(out.get("next_action")), _abi.ptr(out.get("next_logp"))
+            u.policy, u.policy_net = ctypes.pointer(pi._struct), ctypes.pointer(self._actor.struct)
+            u.policy_adam, u.critic_adam = ctypes.pointer(self._actor.adam), ctypes.pointer(self._critics[0].adam)
+            arrays = []
+            for y, (net, tg) in enumerate(done):
+                u.critic[y] = ctypes.pointer(self._critic_structs[y])
+                u.critic_net[y] = ctypes.pointer(self._critics[y].struct)
+                u.critic_targ[y] = ctypes.pointer(net._struct)
+                W = (_abi._P * len(tg))(*[w.data_ptr() for w, _ in tg])
+                b = (_abi._P * len(tg))(*[v.data_ptr() for _, v in tg])
+                u.W_targ[y], u.b_targ[y] = W, b
+                arrays += [W, b]
+            u.scale = self._scale_p
+            u.log_alpha, u.alpha = self._la, ctypes.pointer(self._alpha_struct)
+            u.critic_loss, u.actor_loss, u.logp_mean = self._closs, self._aloss, self._lpm
+            u.workspace, u.workspace_bytes = self._ws, self._ws_bytes
+            # (the entry keeps alive what the struct points into, and the objects whose ids are the key)
+            entry = cache[key] = (u, out, hb, arrays, her, pi, done)
+        u, out = entry[0], entry[1]
+        u.gamma, u.tau = gamma, tau
+        u.seed, u.target_entropy = self.seed, self.target_entropy        # read on every call, as actor_step reads them
+        u.draw_counter = her._counter & 0xFFFFFFFFFFFFFFFF
+        u.step_counter = self.counter & 0xFFFFFFFFFFFFFFFF
+        u.history = None if history is None else history.data_ptr()
+        s = stream.cuda_stream if stream is not None else self._raw_stream(self._index)
+        rc = self._lib.ctr_sac_update(u, updates, s)
+        if rc:
+            _abi.check(rc, "ctr_sac_update")
+        her._log_alpha = self.log_alpha    # stays referenced until the next draw: the launches read it
+        her._counter += updates
+        self.counter += updates
+        pi._sources = list(self._actor.params)
+        pi.weights = pi.biases = pi.packed = None
+        for net, tg in done:
+            net._sources = tg
+            net.weights = net.biases = net.packed = None
+        out = dict(out)
+        if history is not None:
+            out["history"] = history
+        return out
+
     def state_dict(self):
         """Adam's state of the three networks as ``Td3Learner.state_dict`` gives it, with the
         temperature (``log_alpha``, ``alpha_state``: cloned) and the noise ``counter``."""

@@ -1079,6 +1079,89 @@ typedef struct ctr_her_sac_t {
 int ctr_her_sample_sac(const ctr_her_t *her, int64_t batch_size, uint64_t seed, uint64_t counter,
                        const ctr_her_batch_t *out, const ctr_her_sac_t *td, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * A run of SAC updates (added within ABI 17: a new symbol, no entry point or struct changes).
+ * ctr_sac_update makes `updates` whole SAC updates on `stream`.  Update i (0-based) leaves, bit for
+ * bit, in every tensor those calls write, what this sequence leaves:
+ *     ctr_her_sample_sac(her, batch_size, draw_seed, draw_counter + i, batch,
+ *                        {policy, critic_targ[0], critic_targ[1], log_alpha, gamma, target, q1_next, ...})
+ *     ctr_td3_critic_step(critic, critic_net, critic_adam, batch->obs, batch->action, scale, target,
+ *                         batch_size, critic_loss, workspace, ...)
+ *     ctr_sac_actor_step(policy, policy_net, policy_adam, critic, the critics' W and b, batch->obs,
+ *                        batch_size, seed, step_counter + i, log_alpha, alpha, target_entropy,
+ *                        actor_loss, logp_mean, workspace, ...)
+ *     ctr_gauss_load(policy, policy_net->W, policy_net->b)      (the blob the next draw's a' comes from)
+ *     ctr_polyak({critic_targ[y], critic_net[y]->W, ->b, W_targ[y], b_targ[y]}, y = 0, 1; tau)
+ * that is: the policy's and both critics' parameters, gradients, m, v and pow; log_alpha, its state
+ * and its gradient; both target critics' float32 tensors; the three blobs; the batch and target
+ * tensors (they hold the last update's draw); the four loss scalars (the last update's values).
+ * Both counter sums are 64-bit and wrap, as ctr_collect_gauss's.  With history (device, [updates][5]
+ * float32) row i also gets update i's critic 1 loss, critic 2 loss, actor loss, logp_mean and
+ * log_alpha after its step (with alpha->learn == 0: the unchanged log_alpha).
+ *
+ * Launches: the sampler's two scans once per call (the call only reads the store, so the prefix
+ * sums of update 0 are every update's), then five per update: the sampler's kernel, the twin
+ * critics' gradient kernel and the policy's gradient kernel as the calls above launch them, and a
+ * tail behind each gradient kernel.  A tail thread owns one 16-B item of a blob -- eight weights or
+ * four bias floats, ctr_actor_load's and ctr_polyak's mapping, which covers every parameter once --
+ * and for its elements sums the slots in slot order, stores the gradient and makes the Adam step
+ * (what one thread per parameter did), then: the critics' tail (second grid dimension: the critic)
+ * makes the soft update of the target with the new online value, stores it and packs the target's
+ * blob item; the policy's tail packs the policy's blob item, and one of its threads makes the
+ * temperature's step.  The soft update runs ahead of the policy's step: that step reads the online
+ * critics, never the targets.  No allocation, no host read, no synchronisation: the call can be
+ * captured into a graph (a replay repeats its draws: the counters are arguments).
+ *
+ * Refused (CTR_EINVAL, before any launch, ctr_last_error names ctr_sac_update): u NULL; updates < 0;
+ * whatever the five calls above refuse (NULL structs, arrays and layers, shapes, the in_dim
+ * relations to the store and between the networks, the LDS limit, tau NaN or outside [0, 1], a
+ * non-finite gamma, rate or target_entropy, the betas and eps, the workspace NULL, misaligned or
+ * smaller than ctr_sac_workspace_bytes for batch_size, batch_size outside 0..65 536); a target
+ * critic whose shape differs from its online critic's; any two of these being the same pointer: a
+ * parameter, gradient, state or pow tensor of the three networks, a target tensor, the three blobs,
+ * log_alpha, its state and gradient, the loss outputs, the batch and target outputs, the workspace,
+ * history, scale (so: every aliasing the calls above refuse, a target tensor or blob shared with an
+ * online one or between the two targets); an output that starts inside history's updates * 20 bytes.
+ * updates == 0 and batch_size == 0 are checked no-ops. */
+typedef struct ctr_sac_update_t {
+    /* the draw (ctr_her_sample_sac) */
+    const ctr_her_t *her;
+    int64_t  batch_size;
+    uint64_t draw_seed, draw_counter;        /* update i draws under draw_counter + i                 */
+    const ctr_her_batch_t *batch;
+    float   *target;                         /* [B] device, required                                   */
+    float   *q1_next, *q2_next;              /* [B] or NULL                                            */
+    float   *next_action;                    /* [B][6] or NULL                                         */
+    float   *next_logp;                      /* [B] or NULL                                            */
+    float    gamma;
+    float    tau;
+    /* the policy: its 12-row shape and blob, its f32 masters and Adam state */
+    const ctr_actor_t     *policy;
+    const ctr_ddpg_net_t  *policy_net;
+    const ctr_ddpg_adam_t *policy_adam;
+    /* the critics (shapes; their blobs are not read), their masters and their one Adam */
+    const ctr_critic_t    *critic[2];
+    const ctr_ddpg_net_t  *critic_net[2];
+    const ctr_ddpg_adam_t *critic_adam;
+    const float *scale;                      /* device [6] or NULL, as ctr_td3_critic_step's           */
+    /* the target critics: shape and blob, and their f32 tensors, [n_hidden + 1] layers each */
+    const ctr_critic_t *critic_targ[2];
+    float *const *W_targ[2];
+    float *const *b_targ[2];
+    /* the policy step's noise, the temperature */
+    uint64_t seed, step_counter;             /* update i samples under step_counter + i                */
+    float   *log_alpha;
+    const ctr_sac_alpha_t *alpha;
+    float    target_entropy;
+    int32_t  pad;
+    /* outputs (device): critic_loss float[2] or NULL, actor_loss and logp_mean float or NULL */
+    float   *critic_loss, *actor_loss, *logp_mean;
+    void    *workspace;                      /* ctr_sac_workspace_bytes(policy, critic[0], critic[1], max_B) */
+    int64_t  workspace_bytes;
+    float   *history;                        /* [updates][5] or NULL                                   */
+} ctr_sac_update_t;
+int ctr_sac_update(const ctr_sac_update_t *u, int32_t updates, void *stream);
+
 /* CtrReachEnv.reset for the environments with mask[i] != 0 (mask NULL = all).
  * goal [n][3] or NULL (sample a goal), system [n] or NULL (sample uniformly).
  * Writes the reset observation to obs [n][obs_dim]. */
