@@ -91,9 +91,20 @@ launches each instead of nine, the sampler's scans once per iteration, and no ho
 updates.  The iteration's losses come from ``hist`` ([updates, 5]: the two critic losses, the policy's
 loss, logp_mean, log_alpha per update) in the iteration's one host read.
 
+With ``--update-run`` (``main(..., update_run=True)``; DDPG and ``--td3``; it implies ``--device-update``; a
+ValueError with ``--sac``, whose flag is ``--update-call``) the inner loop of DDPG or TD3 is one call as well,
+``learner.update(her, actor_targ, [(actor_targ, policy_targ), (critic_targ_dev, critic_targ), ...], batch_size,
+GAMMA, TAU, updates=updates_per_iter, actor=actor, history=hist)`` (ctr_ddpg_update; TD3 also passes
+``TARGET_NOISE``, ``NOISE_CLIP`` and ``POLICY_DELAY``): the same updates bit for bit, five launches for an
+update with a policy step and three for one without, the sampler's scans once per iteration, no ``polyak_``
+and no ``actor.load_`` (``actor``'s blob is repacked by every policy step).  The iteration's losses come from
+``hist`` ([updates, 2] or [updates, 3]: the critic losses, then the actor loss of the updates that made a
+policy step).
+
 usage: python examples/train_ddpg_her.py [--num-envs N] [--iterations I] [--steps-per-iter S]
            [--batch-size B] [--updates-per-iter U] [--hidden 64,64] [--seed 0] [--device cuda]
-           [--device-targets] [--device-polyak] [--device-update] [--td3] [--sac] [--device-collect] [--update-call]"""
+           [--device-targets] [--device-polyak] [--device-update] [--td3] [--sac] [--device-collect] [--update-call]
+           [--update-run]"""
 import argparse
 import os
 import sys
@@ -128,18 +139,21 @@ def mlp(n_in, hidden, n_out, tanh):
 
 def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, updates_per_iter=40, hidden=(64, 64), seed=0,
          device="cuda", device_targets=False, device_polyak=False, device_update=False, td3=False, sac=False,
-         device_collect=False, update_call=False):
+         device_collect=False, update_call=False, update_run=False):
     if sac and td3:
         raise ValueError("--sac and --td3 are two algorithms: choose one")
     if device_collect and not sac:
         raise ValueError("--device-collect is SAC's collection (venv.collect_gauss): use it with --sac")
     if update_call and not sac:
         raise ValueError("--update-call is SAC's update (SacLearner.update): use it with --sac")
+    if update_run and sac:
+        raise ValueError("--update-run is DDPG's and TD3's update (DdpgLearner.update, Td3Learner.update): SAC's is "
+                         "--update-call")
     if sac:
         return main_sac(num_envs, iterations, steps_per_iter, batch_size, updates_per_iter, hidden, seed, device,
                         device_targets or update_call, device_collect, update_call)
     device = torch.device(device)
-    device_update = device_update or td3
+    device_update = device_update or td3 or update_run
     device_polyak = device_polyak or device_update
     device_targets = device_targets or device_polyak
     torch.manual_seed(seed)
@@ -188,8 +202,25 @@ def main(num_envs=4096, iterations=50, steps_per_iter=20, batch_size=256, update
         critic2_targ_dev = MlpCritic.from_torch(critic2_targ, device)
     losses = []
     updates = 0
+    hist = torch.zeros((updates_per_iter, 3 if td3 else 2), dtype=torch.float32, device=device) if update_run else None
     for it in range(iterations):
         venv.collect(actor, steps_per_iter, noise)
+        if update_run:                                                       # the iteration's updates: one call
+            if td3:
+                first = -(learner.update_count + 1) % POLICY_DELAY           # the first update with a policy step
+                learner.update(her, actor_targ, [(actor_targ, policy_targ), (critic_targ_dev, critic_targ),
+                                                 (critic2_targ_dev, critic2_targ)], batch_size, GAMMA, TAU, TARGET_NOISE,
+                               NOISE_CLIP, POLICY_DELAY, updates=updates_per_iter, actor=actor, history=hist)
+                stepped = hist[first::POLICY_DELAY, 2]
+                # the iteration's only host read
+                c, p = torch.stack((0.5 * hist[:, :2].sum(), stepped.sum())).tolist()
+                losses.append((c / max(updates_per_iter, 1), p / max(stepped.numel(), 1)))
+            else:
+                learner.update(her, actor_targ, [(actor_targ, policy_targ), (critic_targ_dev, critic_targ)], batch_size,
+                               GAMMA, TAU, updates=updates_per_iter, actor=actor, history=hist)
+                h = hist.sum(0).tolist()                                     # the iteration's only host read
+                losses.append((h[0] / max(updates_per_iter, 1), h[1] / max(updates_per_iter, 1)))
+            continue
         critic_sum = torch.zeros((), device=device)
         policy_sum = torch.zeros((), device=device)
         policy_updates = 0
@@ -346,10 +377,13 @@ if __name__ == "__main__":
                          "launch per refill period instead of two per step")
     ap.add_argument("--update-call", action="store_true",
                     help="with --sac: an iteration's updates from one learner.update call (implies --device-targets)")
+    ap.add_argument("--update-run", action="store_true",
+                    help="DDPG and --td3: an iteration's updates from one learner.update call (implies --device-update)")
     args = ap.parse_args()
     out = main(args.num_envs, args.iterations, args.steps_per_iter, args.batch_size, args.updates_per_iter,
                tuple(int(w) for w in args.hidden.split(",")), args.seed, args.device, args.device_targets,
-               args.device_polyak, args.device_update, args.td3, args.sac, args.device_collect, args.update_call)
+               args.device_polyak, args.device_update, args.td3, args.sac, args.device_collect, args.update_call,
+               args.update_run)
     for it, (c, p) in enumerate(out["losses"]):
         print("iteration %3d: critic loss %.4g, policy loss %.4g" % (it, c, p))
     if args.sac:

@@ -3251,3 +3251,4 @@ int ctr_follow(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_
 #include "ctr_ddpg.inc"
 #include "ctr_sac.inc"
 #include "ctr_sac_update.inc"
+#include "ctr_ddpg_update.inc"

@@ -235,7 +235,7 @@ EXPORTED = ("ctr_abi_version", "ctr_last_error", "ctr_fk", "ctr_set_action", "ct
             "ctr_ddpg_workspace_bytes", "ctr_ddpg_critic_step", "ctr_ddpg_actor_step", "ctr_her_sample_td3",
             "ctr_td3_workspace_bytes", "ctr_td3_critic_step", "ctr_gauss_blob_bytes", "ctr_gauss_pack", "ctr_gauss_load",
             "ctr_gauss_act", "ctr_sac_workspace_bytes", "ctr_sac_actor_step", "ctr_her_sample_sac", "ctr_collect_gauss",
-            "ctr_sac_update")
+            "ctr_sac_update", "ctr_ddpg_update")
 
 _lib = None
 

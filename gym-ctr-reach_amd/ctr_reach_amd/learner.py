@@ -11,7 +11,9 @@ parameters.  No autograd and no torch optimiser:
 
 ``Td3Learner`` is the same learner with TD3's two critics, both regressed by one call
 (ctr_td3_critic_step).  ``SacLearner`` is SAC: the same twin critic step, and the stochastic policy's
-step under both critics with the learned temperature (ctr_sac_actor_step).  ``adam_reference`` is the
+step under both critics with the learned temperature (ctr_sac_actor_step).  Each learner's ``update``
+makes a run of whole updates from one C call (ctr_ddpg_update for DDPG and TD3, ctr_sac_update for SAC),
+bit for bit what the calls above leave.  ``adam_reference`` is the
 numpy float32 restatement of the Adam step (the kernel gives its bits).
 """
 import ctypes
@@ -138,6 +140,159 @@ class _Net(object):
         self.pow.copy_(state["pow"])
 
 
+def _run_check(self, critics, her, actor_targ, targets, batch_size, gamma, tau, updates, actor, history, sigma, clip,
+               policy_delay):
+    """``DdpgLearner.update``'s and ``Td3Learner.update``'s checks (``sample_td``'s or ``sample_td3``'s,
+    ``critic_step``'s, ``polyak_``'s and ``load_``'s), before anything is allocated, converted or written.
+    ``critics``: the learner's critic ``_Net``s.  -> (B, updates, gamma, tau, sigma, clip, policy_delay,
+    [(net, target layers), ...])."""
+    import torch
+    from .policy import MlpActor, MlpCritic
+    dev = self.device
+    nc = len(critics)
+
+    def elsewhere(d):
+        return d.type != dev.type or (None not in (d.index, dev.index) and d.index != dev.index)
+
+    hdev = her.venv.device
+    if elsewhere(hdev):
+        raise ValueError("update: the buffer is on %s, the learner on %s" % (hdev, dev))
+    shape = "[(actor_targ, policy_targ), (critic_targ_dev, critic_targ)]" if nc == 1 else \
+        "[(actor_targ, policy_targ), (critic1_targ_dev, critic1_targ), (critic2_targ_dev, critic2_targ)]"
+    targets = [tuple(t) for t in targets]
+    if len(targets) != 1 + nc or any(len(t) != 2 for t in targets):
+        raise ValueError("update: targets is " + shape)
+    if not isinstance(actor_targ, MlpActor):
+        raise ValueError("update: actor_targ must be an MlpActor, not %s" % type(actor_targ).__name__)
+    if targets[0][0] is not actor_targ:
+        raise ValueError("update: targets[0] is (actor_targ, policy_targ): its net is not actor_targ")
+    for m, (net, _) in enumerate(targets[1:]):
+        if not isinstance(net, MlpCritic):
+            raise ValueError("update: target %d must be an MlpCritic, not %s" % (m + 1, type(net).__name__))
+    if actor is not None and not isinstance(actor, MlpActor):
+        raise ValueError("update: actor must be an MlpActor or None, not %s" % type(actor).__name__)
+    if actor is actor_targ:
+        raise ValueError("update: actor and actor_targ are one MlpActor: each has its own blob")
+    named = [(actor_targ, "target policy")] + [(net, "target %d" % (m + 1)) for m, (net, _) in enumerate(targets[1:])]
+    if actor is not None:
+        named.append((actor, "actor"))
+    for net, name in named:
+        if getattr(net, "blob", None) is None:
+            raise ValueError("update: the %s must be on the device" % name)
+        if elsewhere(net.device):
+            raise ValueError("update: the %s is on %s, the learner on %s" % (name, net.device, dev))
+    if nc == 2 and targets[1][0] is targets[2][0]:
+        raise ValueError("update: the two critic targets are one MlpCritic: each has its own blob")
+    gamma, tau = float(gamma), float(tau)
+    if not np.isfinite(gamma):
+        raise ValueError("update: gamma must be finite")
+    if not 0.0 <= tau <= 1.0:
+        raise ValueError("update: tau must be in [0, 1]")
+    sigma, clip = float(sigma), float(clip)
+    if nc == 2:
+        if not (np.isfinite(sigma) and sigma >= 0.0):
+            raise ValueError("update: sigma must be finite and >= 0")
+        if not clip >= 0.0:
+            raise ValueError("update: clip must be >= 0 (inf: the noise is not clipped)")
+    policy_delay = int(policy_delay)
+    if policy_delay < 1:
+        raise ValueError("update: policy_delay must be >= 1")
+    B, updates = int(batch_size), int(updates)
+    if not 0 <= B <= self.max_batch:
+        raise ValueError("update: batch_size = %d, the learner was built for max_batch = %d" % (B, self.max_batch))
+    if updates < 0:
+        raise ValueError("update: updates must be >= 0")
+    if her.obs_dim + 6 != self.in_dim:
+        raise ValueError("update: the buffer's rows are %d floats, the policy's %d" % (her.obs_dim + 6, self.in_dim))
+    done = []
+    actor_targ._device_layers(self._actor.params, "update: target policy: online ")
+    done.append((actor_targ, actor_targ._device_layers(targets[0][1], "update: target policy: target ", target=True)))
+    for m, (net, target) in enumerate(targets[1:]):
+        net._device_layers(critics[m].params, "update: target %d: online " % (m + 1))
+        done.append((net, net._device_layers(target, "update: target %d: target " % (m + 1), target=True)))
+    if actor is not None:
+        actor._device_layers(self._actor.params, "update: the actor's ")        # load_'s: actor has the masters' shape
+    if history is not None:
+        if not (isinstance(history, torch.Tensor) and history.dtype == torch.float32 and not elsewhere(history.device)
+                and tuple(history.shape) == (updates, 1 + nc) and history.is_contiguous()):
+            raise ValueError("update: history must be a contiguous float32 [updates, %d] = [%d, %d] tensor on %s"
+                             % (1 + nc, updates, 1 + nc, dev))
+    return B, updates, gamma, tau, sigma, clip, policy_delay, done
+
+
+def _run_update(self, critic_structs, critics, her, actor_targ, targets, batch_size, gamma, tau, updates, actor, history,
+                return_next, stream, sigma=0.0, clip=0.0, policy_delay=1, update_index=0):
+    """The work of ``DdpgLearner.update`` and ``Td3Learner.update`` (ctr_ddpg_update) -> (the batch dict,
+    updates)."""
+    import torch
+    from . import _abi_ddpg
+    nc = len(critics)
+    B, updates, gamma, tau, sigma, clip, policy_delay, done = _run_check(
+        self, critics, her, actor_targ, targets, batch_size, gamma, tau, updates, actor, history, sigma, clip, policy_delay)
+    key = (id(her), B, bool(return_next), id(actor), None if actor is None else actor.blob.data_ptr()) + tuple(
+        (id(net), net.blob.data_ptr()) + tuple(t.data_ptr() for pair in tg for t in pair) for net, tg in done)
+    cache = self.__dict__.setdefault("_update_cache", {})
+    entry = cache.get(key)
+    if entry is None:
+        if len(cache) >= 8:
+            cache.clear()
+        _, out, hb = her._batch(B, False)
+        dev = self.device
+        out["target"] = torch.empty(B, dtype=torch.float32, device=dev)
+        if return_next:
+            for name in ("q_next",) if nc == 1 else ("q1_next", "q2_next"):
+                out[name] = torch.empty(B, dtype=torch.float32, device=dev)
+            out["next_action"] = torch.empty((B, 6), dtype=torch.float32, device=dev)
+        u = _abi_ddpg.CtrDdpgUpdate()
+        u.her, u.batch_size, u.draw_seed, u.batch = ctypes.pointer(her._h), B, her._draw_seed(None), ctypes.pointer(hb)
+        u.target, u.next_action = _abi.ptr(out["target"]), _abi.ptr(out.get("next_action"))
+        u.q1_next, u.q2_next = _abi.ptr(out.get("q_next" if nc == 1 else "q1_next")), _abi.ptr(out.get("q2_next"))
+        u.n_critics = nc
+        u.policy, u.policy_net = ctypes.pointer(self._actor_struct), ctypes.pointer(self._actor.struct)
+        u.policy_adam, u.critic_adam = ctypes.pointer(self._actor.adam), ctypes.pointer(critics[0].adam)
+        arrays = []
+        for m, (net, tg) in enumerate(done):
+            W = (_abi._P * len(tg))(*[w.data_ptr() for w, _ in tg])
+            b = (_abi._P * len(tg))(*[v.data_ptr() for _, v in tg])
+            arrays += [W, b]
+            if m == 0:
+                u.actor_targ, u.W_targ_actor, u.b_targ_actor = ctypes.pointer(net._struct), W, b
+                continue
+            y = m - 1
+            u.critic[y] = ctypes.pointer(critic_structs[y])
+            u.critic_net[y] = ctypes.pointer(critics[y].struct)
+            u.critic_targ[y], u.W_targ[y], u.b_targ[y] = ctypes.pointer(net._struct), W, b
+        if actor is not None:
+            u.actor = ctypes.pointer(actor._struct)
+        u.scale = self._scale_p
+        u.critic_loss, u.actor_loss = self._closs, self._aloss
+        u.workspace, u.workspace_bytes = self._ws, self._ws_bytes
+        # (the entry keeps alive what the struct points into, and the objects whose ids are the key)
+        entry = cache[key] = (u, out, hb, arrays, her, actor, done)
+    u, out = entry[0], entry[1]
+    u.gamma, u.tau, u.sigma, u.clip = gamma, tau, sigma, clip
+    u.policy_delay, u.update_index = policy_delay, int(update_index) & 0xFFFFFFFFFFFFFFFF
+    u.draw_counter = her._counter & 0xFFFFFFFFFFFFFFFF
+    u.history = None if history is None else history.data_ptr()
+    s = stream.cuda_stream if stream is not None else self._raw_stream(self._index)
+    rc = self._lib.ctr_ddpg_update(u, updates, s)
+    if rc:
+        _abi.check(rc, "ctr_ddpg_update")
+    her._counter += updates
+    if B and (int(update_index) + updates) // policy_delay > int(update_index) // policy_delay:
+        # a policy step was made: the nets are as polyak_ and load_ leave them
+        for net, tg in done:
+            net._sources = tg
+            net.weights = net.biases = net.packed = None
+        if actor is not None:
+            actor._sources = list(self._actor.params)
+            actor.weights = actor.biases = actor.packed = None
+    out = dict(out)
+    if history is not None:
+        out["history"] = history
+    return out, updates
+
+
 class DdpgLearner(object):
     """``policy``: an ``nn.Sequential`` (Linear, ReLU, ..., Linear, Tanh) and ``critic`` one without
     the Tanh, as ``MlpActor.from_torch`` / ``MlpCritic.from_torch`` take them (or lists of
@@ -256,6 +411,38 @@ class DdpgLearner(object):
         if rc:
             _abi.check(rc, "ctr_ddpg_actor_step")
 
+    def update(self, her, actor_targ, targets, batch_size, gamma, tau, updates=1, actor=None, history=None, return_next=False,
+               stream=None):
+        """``updates`` whole DDPG updates from one call (ctr_ddpg_update): each is what
+
+            batch = her.sample_td(batch_size, actor_targ, critic_targ_dev, gamma)
+            learner.critic_step(batch["obs"], batch["action"], batch["target"])
+            learner.actor_step(batch["obs"])
+            polyak_([(actor_targ, policy, policy_targ), (critic_targ_dev, critic, critic_targ)], tau)
+            actor.load_(policy)                                      # with ``actor``
+
+        leaves, bit for bit, in five launches and without the host work of four or five calls; the
+        sampler's two scans run once per call.  ``her``: the ``HerReplayBuffer``; ``actor_targ``: the
+        target policy's ``MlpActor``; ``targets``: [(actor_targ, policy_targ), (critic_targ_dev,
+        critic_targ)], each a target's device net and the owner of its float32 parameters
+        (``nn.Sequential`` or [(W, b), ...]) as ``polyak_`` takes them; ``actor``: None, or the online
+        policy's ``MlpActor``, whose blob is then repacked from the learner's policy masters by every
+        update.
+
+        Returns ``sample_td``'s dict (with ``return_next`` also q_next and next_action), holding the LAST
+        update's draw.  Its tensors are allocated on the first call for a ``batch_size`` and reused: THE
+        NEXT ``update`` CALL OVERWRITES THEM.  ``history``: None, or a contiguous float32 [updates, 2]
+        tensor on the device; row i gets update i's critic loss and actor loss, and the dict returns it
+        under "history".  ``critic_loss`` and ``actor_loss`` hold the last update's values.
+
+        Every check of the calls is made first (ValueError, nothing converted, nothing written).
+        Afterwards ``her``'s draw counter has advanced by ``updates`` and the target nets and ``actor``
+        are as ``polyak_`` / ``load_`` leave them (sources set, host copies dropped).  Asynchronous: no
+        allocation after the first call, no host read; a captured call repeats its draws on replay.  The
+        call's struct is built once per (her, nets, batch_size) and cached."""
+        return _run_update(self, (self._critic_struct,), (self._critic,), her, actor_targ, targets, batch_size, gamma, tau,
+                           updates, actor, history, return_next, stream)[0]
+
     def state_dict(self):
         """Adam's state of both networks, cloned: {"actor": {"m", "v", "pow"}, "critic": {...}} with
         ``m`` and ``v`` as [(W-shaped, b-shaped), ...] and ``pow`` = [beta1^t, beta2^t]."""
@@ -291,6 +478,7 @@ class Td3Learner(object):
         self._setup(policy, True, 6, critic1, critic2, scale, (("actor_lr", actor_lr), ("critic_lr", critic_lr)), betas, eps,
                     max_batch, alloc, "ctr_td3_workspace_bytes")
         self._actor_step = self._lib.ctr_ddpg_actor_step
+        self.update_count = 0           # the updates made through ``update``: where TD3's delayed steps fall
 
     def _setup(self, policy, tanh, out_rows, critic1, critic2, scale, rates, betas, eps, max_batch, alloc, workspace_fn):
         """The constructor's work, which ``SacLearner`` shares: the checks, the three ``_Net``, the
@@ -399,6 +587,30 @@ class Td3Learner(object):
                               rows.data_ptr(), B, self._aloss, self._ws, self._ws_bytes, s)
         if rc:
             _abi.check(rc, "ctr_ddpg_actor_step")
+
+    def update(self, her, actor_targ, targets, batch_size, gamma, tau, sigma=0.2, clip=0.5, policy_delay=2, updates=1,
+               actor=None, history=None, return_next=False, stream=None):
+        """``updates`` whole TD3 updates from one call (ctr_ddpg_update with two critics): each is what
+
+            batch = her.sample_td3(batch_size, actor_targ, critic1_targ_dev, critic2_targ_dev, gamma, sigma, clip)
+            learner.critic_step(batch["obs"], batch["action"], batch["target"])
+            learner.update_count += 1
+            if learner.update_count % policy_delay == 0:
+                learner.actor_step(batch["obs"])
+                polyak_([(actor_targ, policy, policy_targ), (critic1_targ_dev, critic1, critic1_targ),
+                         (critic2_targ_dev, critic2, critic2_targ)], tau)
+                actor.load_(policy)                                  # with ``actor``
+
+        leaves, bit for bit: five launches for an update with a policy step, three for one without.
+        ``targets`` has three pairs; everything else is ``DdpgLearner.update``'s.  ``update_count`` (a
+        plain attribute, 0 at construction, not part of ``state_dict``) counts the updates made through
+        this method and decides where the delayed steps fall; it advances by ``updates``.  ``history``:
+        [updates, 3]: the two critic losses, then the actor loss, whose entry an update without a
+        policy step leaves untouched.  ``return_next``: q1_next, q2_next and next_action."""
+        out, made = _run_update(self, self._critic_structs, self._critics, her, actor_targ, targets, batch_size, gamma, tau,
+                                updates, actor, history, return_next, stream, sigma, clip, policy_delay, self.update_count)
+        self.update_count += made
+        return out
 
     def state_dict(self):
         """Adam's state of the three networks, cloned: {"actor": {"m", "v", "pow"}, "critic1": {...},

@@ -1162,6 +1162,109 @@ typedef struct ctr_sac_update_t {
 } ctr_sac_update_t;
 int ctr_sac_update(const ctr_sac_update_t *u, int32_t updates, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * A run of DDPG / TD3 updates (added within ABI 17: a new symbol, no entry point or struct changes).
+ * ctr_ddpg_update makes `updates` whole updates on `stream`: DDPG's with n_critics == 1, TD3's with
+ * n_critics == 2.  Update i (0-based) leaves, bit for bit, in every tensor those calls write, what
+ * this sequence leaves:
+ *   n_critics == 1:
+ *     ctr_her_sample_td(her, batch_size, draw_seed, draw_counter + i, batch,
+ *                       {actor_targ, critic_targ[0], gamma, target, q1_next, next_action})
+ *     ctr_ddpg_critic_step(critic[0], critic_net[0], critic_adam, batch->obs, batch->action, scale,
+ *                          target, batch_size, critic_loss, workspace, ...)
+ *   n_critics == 2:
+ *     ctr_her_sample_td3(her, batch_size, draw_seed, draw_counter + i, batch,
+ *                        {actor_targ, critic_targ[0], critic_targ[1], gamma, sigma, clip, target, q1_next, ...})
+ *     ctr_td3_critic_step(critic, critic_net, critic_adam, batch->obs, batch->action, scale, target,
+ *                         batch_size, critic_loss, workspace, ...)
+ *   and then, only if (update_index + i + 1) % policy_delay == 0 (the policy's step):
+ *     ctr_ddpg_actor_step(policy, policy_net, policy_adam, critic[0], critic_net[0]->W, ->b, batch->obs,
+ *                         batch_size, actor_loss, workspace, ...)       (under critic 0's NEW parameters)
+ *     ctr_polyak({actor_targ, policy_net->W, ->b, W_targ_actor, b_targ_actor},
+ *                {critic_targ[y], critic_net[y]->W, ->b, W_targ[y], b_targ[y]}, y < n_critics; tau)
+ *     ctr_actor_load(actor, policy_net->W, policy_net->b)               (if actor is not NULL)
+ * that is: the policy's and every critic's parameters, gradients, m, v and pow; every target's
+ * float32 tensors and blob; the online actor's blob; the batch and target tensors (they hold the last
+ * update's draw); critic_loss (the last update's values) and actor_loss (the last policy step's).
+ * The counter sum is 64-bit and wraps.  With history (device, [updates][1 + n_critics] float32) row i
+ * also gets update i's critic losses and then the actor loss; the actor-loss entry of an update
+ * that makes no policy step is left untouched.  critic[1], critic_net[1], critic_targ[1], W_targ[1],
+ * b_targ[1], q2_next, sigma and clip are read only when n_critics == 2.
+ *
+ * Launches: the sampler's two scans once per call (the call only reads the store), then per update
+ * with a policy step five: the sampler's kernel, the critics' gradient kernel, the critics' tail, the
+ * policy's gradient kernel (k_ddpg_grad, as ctr_ddpg_actor_step launches it) and the policy's tail; per
+ * update without one three: the sampler's kernel, the gradient kernel and the apply kernel of
+ * ctr_ddpg_critic_step / ctr_td3_critic_step as it is (no soft update, no blob to pack).  Only when
+ * the call's LAST update makes no policy step and both critic_loss and history are given, one more
+ * launch of one wave copies the n_critics losses to the history row (the apply kernel has one loss
+ * output).
+ * A tail does for every parameter of its network what the apply kernel does (the slots' sum in slot
+ * order, the gradient's store, Adam), then ctr_polyak's work with the new online value (the lerp, the
+ * target's store, the target blob's 16-B item), the critics' tail with the critic as its second grid
+ * dimension; the policy's tail also packs `actor`'s item.  A workgroup owns 256 consecutive items of
+ * a blob (ctr_polyak's ownership: every parameter has one owner), and inside it the elements are
+ * dealt so that consecutive lanes take consecutive floats of one tensor row -- 256 contiguous bytes
+ * per wave where the items are four k-steps of a hidden layer's tile, 64 otherwise -- instead of
+ * ctr_sac_update's one thread per item; the values a blob takes pass through LDS (8 or 16 KB) and each
+ * thread packs its own item behind a barrier.  The critics' soft update runs ahead of the policy's
+ * step: that step reads the online critic only.  No allocation, no host read, no synchronisation:
+ * the call can be captured into a graph (a replay repeats its draws and its delay pattern: the counter
+ * and update_index are arguments).
+ *
+ * Refused (CTR_EINVAL, before any launch, ctr_last_error names ctr_ddpg_update): u NULL; updates < 0;
+ * n_critics outside 1..2; policy_delay < 1; whatever the calls above refuse (NULL structs, arrays and
+ * layers, shapes, the in_dim relations to the store and between the networks, a non-finite gamma, the
+ * rates, betas and eps, the workspace NULL, misaligned or smaller than ctr_ddpg_workspace_bytes (one
+ * critic) / ctr_td3_workspace_bytes (two) for batch_size, batch_size outside 0..65 536); tau NaN or
+ * outside [0, 1]; with two critics a sigma that is not finite or negative, a clip that is NaN or
+ * negative; a target whose shape differs from its online network's; an actor whose shape differs
+ * from the policy's, or whose blob is NULL or misaligned; any two of these being the same pointer: a
+ * parameter, gradient, state or pow tensor of the networks, a target tensor, the targets' blobs and
+ * the actor's, the loss outputs, the batch and target outputs, the workspace, history, scale; an
+ * output that starts inside history's updates * (1 + n_critics) * 4 bytes.  updates == 0 and
+ * batch_size == 0 are checked no-ops. */
+typedef struct ctr_ddpg_update_t {
+    /* the draw (ctr_her_sample_td / ctr_her_sample_td3) */
+    const ctr_her_t *her;
+    int64_t  batch_size;
+    uint64_t draw_seed, draw_counter;        /* update i draws under draw_counter + i                  */
+    const ctr_her_batch_t *batch;
+    float   *target;                         /* [B] device, required                                   */
+    float   *q1_next, *q2_next;              /* [B] or NULL (one critic: q1_next is q_next)            */
+    float   *next_action;                    /* [B][6] or NULL                                         */
+    float    gamma;
+    float    tau;
+    int32_t  n_critics;                      /* 1: DDPG, 2: TD3                                        */
+    float    sigma, clip;                    /* TD3's target smoothing; read when n_critics == 2       */
+    /* the delay */
+    int32_t  policy_delay;                   /* >= 1                                                   */
+    uint64_t update_index;                   /* the updates made before this call                      */
+    /* the policy: its shape (scale and blob are not read), its f32 masters and Adam state */
+    const ctr_actor_t     *policy;
+    const ctr_ddpg_net_t  *policy_net;
+    const ctr_ddpg_adam_t *policy_adam;
+    /* the critics (shapes; their blobs are not read), their masters and their one Adam */
+    const ctr_critic_t    *critic[2];
+    const ctr_ddpg_net_t  *critic_net[2];
+    const ctr_ddpg_adam_t *critic_adam;
+    const float *scale;                      /* device [6] or NULL, as ctr_ddpg_critic_step's          */
+    /* the targets: shape and blob, and their f32 tensors, [n_hidden + 1] layers each */
+    const ctr_actor_t  *actor_targ;
+    float *const *W_targ_actor;
+    float *const *b_targ_actor;
+    const ctr_critic_t *critic_targ[2];
+    float *const *W_targ[2];
+    float *const *b_targ[2];
+    const ctr_actor_t  *actor;               /* the online actor's shape and blob, or NULL             */
+    /* outputs (device): critic_loss float[n_critics] or NULL, actor_loss float or NULL */
+    float   *critic_loss, *actor_loss;
+    void    *workspace;                      /* ctr_ddpg_workspace_bytes / ctr_td3_workspace_bytes     */
+    int64_t  workspace_bytes;
+    float   *history;                        /* [updates][1 + n_critics] or NULL                       */
+} ctr_ddpg_update_t;
+int ctr_ddpg_update(const ctr_ddpg_update_t *u, int32_t updates, void *stream);
+
 /* CtrReachEnv.reset for the environments with mask[i] != 0 (mask NULL = all).
  * goal [n][3] or NULL (sample a goal), system [n] or NULL (sample uniformly).
  * Writes the reset observation to obs [n][obs_dim]. */
