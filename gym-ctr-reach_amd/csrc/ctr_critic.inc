@@ -281,8 +281,7 @@ int ctr_her_sample_td(const ctr_her_t *her, int64_t batch_size, uint64_t seed, u
     const size_t shm = std::max(ak.bytes, ck.bytes) + ACTOR_LDS_SLACK;
     if (int r = allow_dynamic_lds(k_her_sample_td, shm)) return r;
     const TdK tk = {td->gamma, td->target, td->q_next, td->next_action};
-    hipLaunchKernelGGL(k_her_scan_tiles, dim3((unsigned)tiles), dim3(BLOCK), 0, (hipStream_t)stream, HerK{*her});
-    hipLaunchKernelGGL(k_her_scan_tops, dim3(1), dim3(BLOCK), 0, (hipStream_t)stream, HerK{*her}, tiles);
+    her_scan(her, tiles, stream);
     hipLaunchKernelGGL(k_her_sample_td, dim3(grid_for(batch_size)), dim3(BLOCK), shm, (hipStream_t)stream, HerK{*her},
                        batch_size, seed, counter, *out, ak, ck, tk);
     return hip_check("ctr_her_sample_td launch");
@@ -317,8 +316,7 @@ int ctr_her_sample_td3(const ctr_her_t *her, int64_t batch_size, uint64_t seed, 
     const size_t shm = std::max(ak.bytes, std::max(ck1.bytes, ck2.bytes)) + ACTOR_LDS_SLACK;
     if (int r = allow_dynamic_lds(k_her_sample_td3, shm)) return r;
     const Td3K tk = {td->gamma, td->sigma, td->clip, td->target, td->q1_next, td->q2_next, td->next_action};
-    hipLaunchKernelGGL(k_her_scan_tiles, dim3((unsigned)tiles), dim3(BLOCK), 0, (hipStream_t)stream, HerK{*her});
-    hipLaunchKernelGGL(k_her_scan_tops, dim3(1), dim3(BLOCK), 0, (hipStream_t)stream, HerK{*her}, tiles);
+    her_scan(her, tiles, stream);
     hipLaunchKernelGGL(k_her_sample_td3, dim3(grid_for(batch_size)), dim3(BLOCK), shm, (hipStream_t)stream, HerK{*her},
                        batch_size, seed, counter, *out, ak, ck1, ck2, tk);
     return hip_check("ctr_her_sample_td3 launch");

@@ -396,24 +396,33 @@ __device__ __forceinline__ float ddpg_adam(float p, float g, float &m, float &v,
     return p - step;
 }
 
+// Element 0's duties behind a gradient launch, in the apply kernels and in the update calls' tails
+// (ctr_sac_update.inc, ctr_ddpg_update.inc): the advanced powers to pow, and the slots' loss partials,
+// summed in slot order and scaled, to loss and to a history entry (either may be NULL; hist by reference:
+// a tail's is a kernel argument, read where it is used).
+__device__ __forceinline__ void ddpg_apply_head(const DdpgApplyK &k, float *const &hist, float pw1, float pw2)
+{
+    k.pow[0] = pw1;
+    k.pow[1] = pw2;
+    if (k.loss || hist) {
+        const double *lpart = reinterpret_cast<const double *>(k.ws + 16);
+        double s = lpart[0];
+        for (int t = 1; t < k.slots; ++t) s += lpart[t];
+        const float loss = (float)(s * k.loss_scale);
+        if (k.loss) *k.loss = loss;
+        if (hist) *hist = loss;
+    }
+}
+
 // The apply launch's work of one thread: element blockIdx.x * BLOCK + threadIdx.x of k's network.
 __device__ __forceinline__ void ddpg_apply_element(const DdpgApplyK &k)
 {
     const float *hdr = reinterpret_cast<const float *>(k.ws);
     const float *part = reinterpret_cast<const float *>(k.ws + DDPG_HDR);
     const int64_t stride = ddpg_slot_floats(k.params, k.biases);
-    const double *lpart = reinterpret_cast<const double *>(k.ws + 16);
     const int e = (int)(blockIdx.x * BLOCK + threadIdx.x);
     const float pw1 = hdr[0], pw2 = hdr[1];
-    if (e == 0) {
-        k.pow[0] = pw1;
-        k.pow[1] = pw2;
-        if (k.loss) {
-            double s = lpart[0];
-            for (int i = 1; i < k.slots; ++i) s += lpart[i];
-            *k.loss = (float)(s * k.loss_scale);
-        }
-    }
+    if (e == 0) ddpg_apply_head(k, nullptr, pw1, pw2);
     if (e >= k.params) return;
     // the element's tensor; the arrays by constant index (they are kernel arguments)
     int firstf = 0, tensor = 0;
@@ -564,19 +573,64 @@ int ddpg_learn_check(const char *fn, const ctr_ddpg_net_t *net, const ctr_ddpg_a
     return 0;
 }
 
-template <bool ACTOR>
-int ddpg_launch(const char *fn, DdpgGradK &gk, DdpgApplyK &ap, void *stream)
+// The critics of a step (nc: 1, or 2 for the twins), each entry in turn: its shape, then the two of one
+// in_dim; critic 0's workspace region as ctr_ddpg_critic_step lays it out, critic 1's behind it (a region
+// is a multiple of 16 B), and ddpg_learn_check on each.  null_entry: the caller's words for a NULL
+// critic[y] or net[y] (reached from ctr_ddpg_update only, which looks at entry and shape critic by critic; the
+// twin callers have refused a NULL entry of either critic before they call); twin_ws: the workspace
+// function its message names when the second region does not fit.
+int ddpg_critics_check(const char *fn, int nc, const ctr_critic_t *const *critic, const ctr_ddpg_net_t *const *net,
+                       const ctr_ddpg_adam_t *adam, int64_t B, void *workspace, int64_t workspace_bytes,
+                       const char *null_entry, const char *twin_ws, DdpgGradK *gk, DdpgApplyK *ap)
 {
-    constexpr size_t MAX_SHM = 2 * (size_t)DDPG_T * (DDPG_X0 + DDPG_OUTC + 2 * DDPG_PAD + CTR_ACTOR_MAX_HIDDEN *
-                                                     (CTR_ACTOR_MAX_WIDTH + DDPG_PAD)) * sizeof(float) + ACTOR_LDS_SLACK;
-    static_assert(MAX_SHM + DDPG_T * sizeof(float) <= LDS_PER_WORKGROUP, "every actor with every critic fits in LDS");
-    const size_t shm = ((ACTOR ? ddpg_lds_floats(gk.net) + ddpg_lds_floats(gk.crit) : ddpg_lds_floats(gk.net))) * sizeof(float) +
-                       ACTOR_LDS_SLACK;
-    if (int r = allow_dynamic_lds(k_ddpg_grad<ACTOR>, shm)) return r;
+    static_assert(DDPG_HDR % 16 == 0, "a region is a multiple of 16 B");
+    for (int y = 0; y < nc; ++y) {
+        if (!critic[y] || !net[y]) return ddpg_fail(fn, null_entry);
+        if (int r = ddpg_shape_check(fn, nullptr, critic[y], false, nullptr, &gk[y].net)) return r;
+    }
+    if (nc == 2 && gk[0].net.in_dim != gk[1].net.in_dim) return ddpg_fail(fn, "the two critics must have the same in_dim");
+    const int64_t Bc = B < 0 ? 0 : std::min(B, DDPG_MAX_B);
+    const int64_t off = ddpg_ws_bytes(gk[0].net.params, gk[0].net.biases, Bc);
+    if (int r = ddpg_learn_check(fn, net[0], adam, B, workspace, workspace_bytes, &gk[0].net, &ap[0])) return r;
+    if (nc == 1) return 0;
+    if (workspace_bytes < off + ddpg_ws_bytes(gk[1].net.params, gk[1].net.biases, Bc)) return ddpg_fail(fn, twin_ws);
+    return ddpg_learn_check(fn, net[1], adam, B, static_cast<char *>(workspace) + off, workspace_bytes - off, &gk[1].net, &ap[1]);
+}
+
+// What a gradient launch (DdpgGradK, SacGradK) takes from its network's checked DdpgApplyK.
+template <class GradK>
+void ddpg_grad_state(GradK &gk, const DdpgApplyK &ap)
+{
     gk.beta1 = ap.beta1;
     gk.beta2 = ap.beta2;
     gk.pow = ap.pow;
     gk.ws = const_cast<char *>(ap.ws);
+}
+
+// A checked critic's launch arguments for a batch of B > 0 rows -> the dynamic LDS bytes of its gradient launch.
+size_t ddpg_critic_fill(DdpgGradK &gk, DdpgApplyK &ap, const float *rows, const float *actions, const float *scale,
+                        const float *target, int64_t B, float *loss)
+{
+    gk.rows = rows;
+    gk.actions = actions;
+    gk.scale = scale;
+    gk.target = target;
+    gk.B = (int32_t)B;
+    gk.dq = (float)(2.0 / (double)B);
+    ddpg_grad_state(gk, ap);
+    ap.loss_scale = 1.0 / (double)B;
+    ap.loss = loss;
+    return ddpg_lds_floats(gk.net) * sizeof(float) + ACTOR_LDS_SLACK;
+}
+
+// The two launches of a single step; shm: the gradient launch's dynamic LDS bytes.
+template <bool ACTOR>
+int ddpg_launch(const char *fn, const DdpgGradK &gk, const DdpgApplyK &ap, size_t shm, void *stream)
+{
+    constexpr size_t MAX_SHM = 2 * (size_t)DDPG_T * (DDPG_X0 + DDPG_OUTC + 2 * DDPG_PAD + CTR_ACTOR_MAX_HIDDEN *
+                                                     (CTR_ACTOR_MAX_WIDTH + DDPG_PAD)) * sizeof(float) + ACTOR_LDS_SLACK;
+    static_assert(MAX_SHM + DDPG_T * sizeof(float) <= LDS_PER_WORKGROUP, "every actor with every critic fits in LDS");
+    if (int r = allow_dynamic_lds(k_ddpg_grad<ACTOR>, shm)) return r;
     hipLaunchKernelGGL(k_ddpg_grad<ACTOR>, dim3((unsigned)ap.slots), dim3(BLOCK), shm, (hipStream_t)stream, gk);
     hipLaunchKernelGGL(k_ddpg_apply, dim3(grid_for(ap.params)), dim3(BLOCK), 0, (hipStream_t)stream, ap);
     char what[64];
@@ -610,15 +664,8 @@ int ctr_ddpg_critic_step(const ctr_critic_t *critic, const ctr_ddpg_net_t *net, 
     if (int r = ddpg_learn_check(fn, net, adam, B, workspace, workspace_bytes, &gk.net, &ap)) return r;
     if (B > 0 && (!rows || !actions || !target)) return ddpg_fail(fn, "rows, actions or target is NULL");
     if (B == 0) return 0;
-    gk.rows = rows;
-    gk.actions = actions;
-    gk.scale = scale;
-    gk.target = target;
-    gk.B = (int32_t)B;
-    gk.dq = (float)(2.0 / (double)B);
-    ap.loss_scale = 1.0 / (double)B;
-    ap.loss = loss;
-    return ddpg_launch<false>(fn, gk, ap, stream);
+    const size_t shm = ddpg_critic_fill(gk, ap, rows, actions, scale, target, B, loss);
+    return ddpg_launch<false>(fn, gk, ap, shm, stream);
 }
 
 int ctr_ddpg_actor_step(const ctr_actor_t *actor, const ctr_ddpg_net_t *net, const ctr_ddpg_adam_t *adam,
@@ -641,9 +688,11 @@ int ctr_ddpg_actor_step(const ctr_actor_t *actor, const ctr_ddpg_net_t *net, con
     gk.rows = rows;
     gk.B = (int32_t)B;
     gk.dq = (float)(-1.0 / (double)B);
+    ddpg_grad_state(gk, ap);
     ap.loss_scale = -1.0 / (double)B;
     ap.loss = loss;
-    return ddpg_launch<true>(fn, gk, ap, stream);
+    const size_t shm = (ddpg_lds_floats(gk.net) + ddpg_lds_floats(gk.crit)) * sizeof(float) + ACTOR_LDS_SLACK;
+    return ddpg_launch<true>(fn, gk, ap, shm, stream);
 }
 
 int64_t ctr_td3_workspace_bytes(const ctr_actor_t *actor, const ctr_critic_t *critic1, const ctr_critic_t *critic2,
@@ -670,19 +719,10 @@ int ctr_td3_critic_step(const ctr_critic_t *const critic[2], const ctr_ddpg_net_
     DdpgGradK gk[2] = {};
     DdpgApplyK ap[2];
     if (!critic || !net) return ddpg_fail(fn, "critic or net is NULL");
-    if (!critic[0] || !critic[1] || !net[0] || !net[1]) return ddpg_fail(fn, "NULL entry in critic[2] or net[2]");
-    if (int r = ddpg_shape_check(fn, nullptr, critic[0], false, nullptr, &gk[0].net)) return r;
-    if (int r = ddpg_shape_check(fn, nullptr, critic[1], false, nullptr, &gk[1].net)) return r;
-    if (gk[0].net.in_dim != gk[1].net.in_dim) return ddpg_fail(fn, "the two critics must have the same in_dim");
-    // critic 0's region as ctr_ddpg_critic_step lays it out, critic 1's behind it (a region is a multiple of 16 B)
-    static_assert(DDPG_HDR % 16 == 0, "a region is a multiple of 16 B");
-    const int64_t Bc = B < 0 ? 0 : std::min(B, DDPG_MAX_B);
-    const int64_t off = ddpg_ws_bytes(gk[0].net.params, gk[0].net.biases, Bc);
-    if (int r = ddpg_learn_check(fn, net[0], adam, B, workspace, workspace_bytes, &gk[0].net, &ap[0])) return r;
-    if (workspace_bytes < off + ddpg_ws_bytes(gk[1].net.params, gk[1].net.biases, Bc))
-        return ddpg_fail(fn, "workspace too small (ctr_td3_workspace_bytes)");
-    if (int r = ddpg_learn_check(fn, net[1], adam, B, static_cast<char *>(workspace) + off, workspace_bytes - off,
-                                 &gk[1].net, &ap[1]))
+    const char *null_entry = "NULL entry in critic[2] or net[2]";
+    if (!critic[0] || !critic[1] || !net[0] || !net[1]) return ddpg_fail(fn, null_entry);
+    if (int r = ddpg_critics_check(fn, 2, critic, net, adam, B, workspace, workspace_bytes, null_entry,
+                                   "workspace too small (ctr_td3_workspace_bytes)", gk, ap))
         return r;
     // the planes run side by side: nothing one of them writes may belong to the other
     const int nt0 = 2 * (gk[0].net.n_hidden + 1), nt1 = 2 * (gk[1].net.n_hidden + 1);
@@ -700,21 +740,8 @@ int ctr_td3_critic_step(const ctr_critic_t *const critic[2], const ctr_ddpg_net_
     if (B > 0 && (!rows || !actions || !target)) return ddpg_fail(fn, "rows, actions or target is NULL");
     if (B == 0) return 0;
     size_t shm = 0;
-    for (int y = 0; y < 2; ++y) {
-        gk[y].rows = rows;
-        gk[y].actions = actions;
-        gk[y].scale = scale;
-        gk[y].target = target;
-        gk[y].B = (int32_t)B;
-        gk[y].dq = (float)(2.0 / (double)B);
-        gk[y].beta1 = ap[y].beta1;
-        gk[y].beta2 = ap[y].beta2;
-        gk[y].pow = ap[y].pow;
-        gk[y].ws = const_cast<char *>(ap[y].ws);
-        ap[y].loss_scale = 1.0 / (double)B;
-        ap[y].loss = loss ? loss + y : nullptr;
-        shm = std::max(shm, ddpg_lds_floats(gk[y].net) * sizeof(float) + ACTOR_LDS_SLACK);
-    }
+    for (int y = 0; y < 2; ++y)
+        shm = std::max(shm, ddpg_critic_fill(gk[y], ap[y], rows, actions, scale, target, B, loss ? loss + y : nullptr));
     if (int r = allow_dynamic_lds(k_td3_grad, shm)) return r;
     const unsigned gx = grid_for(std::max(ap[0].params, ap[1].params));
     hipLaunchKernelGGL(k_td3_grad, dim3((unsigned)ap[0].slots, 2), dim3(BLOCK), shm, (hipStream_t)stream, gk[0], gk[1]);

@@ -1,6 +1,7 @@
 // ctr_ddpg_update.inc -- a run of DDPG or TD3 updates from one call (ctr_ddpg_update;
 // include/ctr_reach_amd.h, "A run of DDPG / TD3 updates": the specification).  Included at the end of
-// ctr_kernels.hip, after ctr_sac_update.inc.
+// ctr_kernels.hip, after ctr_update_common.inc (the tails' arguments and tensor selection, the host checks
+// both update calls share) and ctr_sac_update.inc.
 //
 // An update with a policy step is what ctr_her_sample_td (or _td3), ctr_ddpg_critic_step (or
 // ctr_td3_critic_step), ctr_ddpg_actor_step, ctr_polyak and ctr_actor_load leave, in five launches:
@@ -35,12 +36,8 @@ namespace {
 static_assert(BLOCK == 256, "the deal below is four waves of 64 lanes over 256 items");
 
 struct DdpgTailK {
-    DdpgApplyK ap;
-    ActorK ak;                         // the TARGET's layout and blob
-    float *Wt[ACTOR_LAYERS], *bt[ACTOR_LAYERS];
-    float tau;
+    UpdateTailK t;                     // (t.ak: the TARGET's layout and blob)
     void *online_blob;                 // the actor's tail: the online actor's blob (the target's layout), or NULL
-    float *hist;                       // the history row's entry for this network's loss, or NULL
 };
 
 // The staging's float4 of item q's half (j >> 2) of a blob's BLOCK items.  Plane `half` holds the
@@ -55,27 +52,16 @@ __device__ __forceinline__ int ddpg_tail_slot(int q, int half)
 // A tail's work of one workgroup: items blockIdx.x * BLOCK .. + BLOCK - 1 of k's blob.  s_t, s_p: 8 * BLOCK
 // floats each (s_p: ONLINE only).
 template <bool ONLINE>
-__device__ __forceinline__ void ddpg_tail_group(const DdpgTailK &k, float *s_t, float *s_p)
+__device__ __forceinline__ void ddpg_tail_group(const DdpgTailK &kd, float *s_t, float *s_p)
 {
+    const UpdateTailK &k = kd.t;
     const DdpgApplyK &a = k.ap;
     const float *hdr = reinterpret_cast<const float *>(a.ws);
     const uint32_t i0 = blockIdx.x * BLOCK, items = k.ak.bytes / 16;
     const float pw1 = hdr[0], pw2 = hdr[1];
-    if (i0 + threadIdx.x == 0) {
-        // element 0's duties
-        a.pow[0] = pw1;
-        a.pow[1] = pw2;
-        if (a.loss || k.hist) {
-            const double *lpart = reinterpret_cast<const double *>(a.ws + 16);
-            double s = lpart[0];
-            for (int t = 1; t < a.slots; ++t) s += lpart[t];
-            const float loss = (float)(s * a.loss_scale);
-            if (a.loss) *a.loss = loss;
-            if (k.hist) *k.hist = loss;
-        }
-    }
+    if (i0 + threadIdx.x == 0) ddpg_apply_head(a, k.hist, pw1, pw2);
     if (i0 >= items) return;           // (the whole group: a plane past its blob)
-    const bool online = ONLINE && k.online_blob != nullptr;
+    const bool online = ONLINE && kd.online_blob != nullptr;
     const float *part = reinterpret_cast<const float *>(a.ws + DDPG_HDR);
     const int64_t stride = ddpg_slot_floats(a.params, a.biases);
     // the deal: this thread's item-wave, lane half and element, and its wave's first row
@@ -96,43 +82,29 @@ __device__ __forceinline__ void ddpg_tail_group(const DdpgTailK &k, float *s_t, 
         }
         float x = 0.f, xp = 0.f;       // what the blobs take: +0 for the padding
         if (idx >= 0) {
-            // the item's tensors; the arrays by constant index (they are kernel arguments: a selection
-            // by a runtime index becomes a table of the pointers in scratch)
-            int first = 0, bo = a.boff[0];
-            float *p = a.p[0], *gp = a.g[0], *mp = a.m[0], *vp = a.v[0], *tp = k.Wt[0];
-            #pragma unroll
-            for (int l = 0; l < ACTOR_LAYERS; ++l)
-                if (it.l == l) {
-                    first = it.bias ? a.end[2 * l] : (l ? a.end[l ? 2 * l - 1 : 0] : 0);
-                    bo = a.boff[l];
-                    p = it.bias ? a.p[2 * l + 1] : a.p[2 * l];
-                    gp = it.bias ? a.g[2 * l + 1] : a.g[2 * l];
-                    mp = it.bias ? a.m[2 * l + 1] : a.m[2 * l];
-                    vp = it.bias ? a.v[2 * l + 1] : a.v[2 * l];
-                    tp = it.bias ? k.bt[l] : k.Wt[l];
-                }
+            const UpdateTensors ts = update_tensors(k, it);
             float g;
             if (it.bias) {
                 // the slots' f64 sums, rounded once
-                const double *bp = reinterpret_cast<const double *>(part + ddpg_slot_w(a.params)) + bo + idx;
+                const double *bp = reinterpret_cast<const double *>(part + ddpg_slot_w(a.params)) + ts.bo + idx;
                 double s = bp[0];
                 for (int t = 1; t < a.slots; ++t) s += bp[(size_t)t * (stride / 2)];
                 g = (float)s;
             } else {
-                const float *wp = part + first + idx;
+                const float *wp = part + ts.first + idx;
                 g = wp[0];
                 #pragma unroll 8
                 for (int t = 1; t < a.slots; ++t) g += wp[(size_t)t * stride];
             }
-            float m = mp[idx], v = vp[idx];
-            const float told = tp[idx];
-            gp[idx] = g;
-            xp = ddpg_adam(p[idx], g, m, v, a.lr, a.beta1, a.beta2, a.eps, pw1, pw2);
-            p[idx] = xp;
-            mp[idx] = m;
-            vp[idx] = v;
+            float m = ts.mp[idx], v = ts.vp[idx];
+            const float told = ts.tp[idx];
+            ts.gp[idx] = g;
+            xp = ddpg_adam(ts.p[idx], g, m, v, a.lr, a.beta1, a.beta2, a.eps, pw1, pw2);
+            ts.p[idx] = xp;
+            ts.mp[idx] = m;
+            ts.vp[idx] = v;
             x = polyak_lerp(told, xp, k.tau);
-            tp[idx] = x;
+            ts.tp[idx] = x;
         }
         const int s = 4 * ddpg_tail_slot(q, j >> 2) + (j & 3);
         s_t[s] = x;
@@ -151,7 +123,7 @@ __device__ __forceinline__ void ddpg_tail_group(const DdpgTailK &k, float *s_t, 
         const float4 plo = *reinterpret_cast<const float4 *>(s_p + 4 * ddpg_tail_slot(q, 0));
         const float4 phi = *reinterpret_cast<const float4 *>(s_p + 4 * ddpg_tail_slot(q, 1));
         const float vp[8] = {plo.x, plo.y, plo.z, plo.w, phi.x, phi.y, phi.z, phi.w};
-        static_cast<uint4 *>(k.online_blob)[i0 + q] = actor_item_pack(it, vp);
+        static_cast<uint4 *>(kd.online_blob)[i0 + q] = actor_item_pack(it, vp);
     }
 }
 
@@ -177,20 +149,6 @@ __global__ __launch_bounds__(BLOCK) void k_ddpg_actor_tail(DdpgTailK k)
 __global__ __launch_bounds__(64) void k_ddpg_loss_copy(const float *loss, float *hist, int n)
 {
     if ((int)threadIdx.x < n) hist[threadIdx.x] = loss[threadIdx.x];
-}
-
-int ddpg_update_fail(const char *a, const char *b)
-{
-    snprintf(g_err, sizeof g_err, "ctr_ddpg_update: %s and %s are the same memory", a, b);
-    return CTR_EINVAL;
-}
-
-// A target's layout against its online network's shape.
-bool ddpg_same_shape(const ActorK &t, const DdpgNetK &n)
-{
-    bool same = t.in_dim == n.in_dim && t.n_hidden == n.n_hidden;
-    for (int l = 0; same && l < n.n_hidden; ++l) same = 32 * t.tiles[l] == n.width[l];
-    return same;
 }
 
 }  // namespace
@@ -229,22 +187,10 @@ int ctr_ddpg_update(const ctr_ddpg_update_t *u, int32_t updates, void *stream)
     // ---- ctr_ddpg_critic_step's / ctr_td3_critic_step's, on the batch's obs, action and the target
     DdpgGradK gk[2] = {};
     DdpgApplyK ap[2] = {};
-    for (int y = 0; y < nc; ++y) {
-        if (!u->critic[y] || !u->critic_net[y]) return ddpg_fail(fn, "NULL entry in critic[n_critics] or critic_net[n_critics]");
-        if (int r = ddpg_shape_check(fn, nullptr, u->critic[y], false, nullptr, &gk[y].net)) return r;
-    }
-    if (nc == 2 && gk[0].net.in_dim != gk[1].net.in_dim) return ddpg_fail(fn, "the two critics must have the same in_dim");
-    const int64_t Bc = std::min(B, DDPG_MAX_B);
-    const int64_t off = ddpg_ws_bytes(gk[0].net.params, gk[0].net.biases, Bc);
-    if (int r = ddpg_learn_check(fn, u->critic_net[0], u->critic_adam, B, u->workspace, u->workspace_bytes, &gk[0].net, &ap[0]))
+    if (int r = ddpg_critics_check(fn, nc, u->critic, u->critic_net, u->critic_adam, B, u->workspace, u->workspace_bytes,
+                                   "NULL entry in critic[n_critics] or critic_net[n_critics]",
+                                   "workspace too small (ctr_td3_workspace_bytes)", gk, ap))
         return r;
-    if (nc == 2) {
-        if (u->workspace_bytes < off + ddpg_ws_bytes(gk[1].net.params, gk[1].net.biases, Bc))
-            return ddpg_fail(fn, "workspace too small (ctr_td3_workspace_bytes)");
-        if (int r = ddpg_learn_check(fn, u->critic_net[1], u->critic_adam, B, static_cast<char *>(u->workspace) + off,
-                                     u->workspace_bytes - off, &gk[1].net, &ap[1]))
-            return r;
-    }
     // ---- ctr_ddpg_actor_step's, on the batch's obs under critic 0
     DdpgGradK pg = {};
     DdpgApplyK pp;
@@ -256,18 +202,16 @@ int ctr_ddpg_update(const ctr_ddpg_update_t *u, int32_t updates, void *stream)
     }
     // ---- ctr_polyak's, the targets against their online networks, ctr_actor_load's
     if (!(u->tau >= 0.f && u->tau <= 1.f)) return ddpg_fail(fn, "tau must be in [0, 1]");
-    if (!ddpg_same_shape(atk, pg.net)) return ddpg_fail(fn, "the target policy's shape differs from the policy's");
-    if (!u->W_targ_actor || !u->b_targ_actor) return ddpg_fail(fn, "W_targ_actor or b_targ_actor is NULL");
-    for (int l = 0; l <= pg.net.n_hidden; ++l)
-        if (!u->W_targ_actor[l] || !u->b_targ_actor[l])
-            return ddpg_fail(fn, "NULL layer among W_targ_actor, b_targ_actor [0..n_hidden]");
-    for (int y = 0; y < nc; ++y) {
-        const DdpgNetK &cn = gk[y].net;
-        if (!ddpg_same_shape(tk[y], cn)) return ddpg_fail(fn, "a target critic's shape differs from its online critic's");
-        if (!u->W_targ[y] || !u->b_targ[y]) return ddpg_fail(fn, "NULL entry in W_targ[n_critics] or b_targ[n_critics]");
-        for (int l = 0; l <= cn.n_hidden; ++l)
-            if (!u->W_targ[y][l] || !u->b_targ[y][l]) return ddpg_fail(fn, "NULL layer among W_targ, b_targ [0..n_hidden]");
-    }
+    if (int r = update_target_check(fn, atk, pg.net, u->W_targ_actor, u->b_targ_actor,
+                                    "the target policy's shape differs from the policy's", "W_targ_actor or b_targ_actor is NULL",
+                                    "NULL layer among W_targ_actor, b_targ_actor [0..n_hidden]"))
+        return r;
+    for (int y = 0; y < nc; ++y)
+        if (int r = update_target_check(fn, tk[y], gk[y].net, u->W_targ[y], u->b_targ[y],
+                                        "a target critic's shape differs from its online critic's",
+                                        "NULL entry in W_targ[n_critics] or b_targ[n_critics]",
+                                        "NULL layer among W_targ, b_targ [0..n_hidden]"))
+            return r;
     if (u->actor) {
         if (int r = td_named(fn, actor_layout(u->actor, &ok))) return r;
         if (int r = td_named(fn, mlp_blob("actor", u->actor->blob, &ok))) return r;
@@ -275,62 +219,27 @@ int ctr_ddpg_update(const ctr_ddpg_update_t *u, int32_t updates, void *stream)
     }
     // ---- nothing the call writes is anything else it writes or reads (base pointers, as the replaced
     // calls compare them)
-    static const char *const tn[4] = {"a parameter tensor", "a gradient tensor", "a first-moment tensor", "a second-moment tensor"};
-    SacPtr ptr[3 * (4 * DDPG_TENSORS + 1) + 3 * DDPG_TENSORS + 32];
-    int np = 0;
-    auto add = [&](const void *p, const char *name, bool written) {
-        if (p) ptr[np++] = SacPtr{p, name, written};
-    };
-    const DdpgApplyK *const nets[3] = {&pp, &ap[0], &ap[1]};
+    UpdatePtrs ptrs;
     const int layers[3] = {pg.net.n_hidden + 1, gk[0].net.n_hidden + 1, gk[1].net.n_hidden + 1};
-    for (int n = 0; n < 1 + nc; ++n) {
-        for (int t = 0; t < 2 * layers[n]; ++t) {
-            add(nets[n]->p[t], tn[0], true);
-            add(nets[n]->g[t], tn[1], true);
-            add(nets[n]->m[t], tn[2], true);
-            add(nets[n]->v[t], tn[3], true);
-        }
-        add(nets[n]->pow, "a net's pow", true);
-    }
-    for (int l = 0; l < layers[0]; ++l) {
-        add(u->W_targ_actor[l], "a target tensor", true);
-        add(u->b_targ_actor[l], "a target tensor", true);
-    }
-    for (int y = 0; y < nc; ++y)
-        for (int l = 0; l < layers[1 + y]; ++l) {
-            add(u->W_targ[y][l], "a target tensor", true);
-            add(u->b_targ[y][l], "a target tensor", true);
-        }
-    add(atk.blob, "the target policy's blob", true);
-    for (int y = 0; y < nc; ++y) add(tk[y].blob, "a target critic's blob", true);
-    add(ok.blob, "the online actor's blob", true);
-    add(u->critic_loss, "critic_loss", true);
-    add(u->actor_loss, "actor_loss", true);
-    add(u->workspace, "the workspace", true);
-    add(u->target, "target", true);
-    add(u->q1_next, "q1_next", true);
-    if (nc == 2) add(u->q2_next, "q2_next", true);
-    add(u->next_action, "next_action", true);
-    if (B > 0) {
-        add(u->batch->obs, "batch->obs", true);
-        add(u->batch->action, "batch->action", true);
-        add(u->batch->reward, "batch->reward", true);
-        add(u->batch->next_obs, "batch->next_obs", true);
-        add(u->batch->done, "batch->done", true);
-        add(u->batch->index, "batch->index", true);
-    }
-    add(u->history, "history", true);
-    add(u->scale, "scale", false);
-    std::sort(ptr, ptr + np, [](const SacPtr &a, const SacPtr &b) { return (uintptr_t)a.p < (uintptr_t)b.p; });
-    for (int i = 0; i + 1 < np; ++i)
-        if (ptr[i].p == ptr[i + 1].p) return ddpg_update_fail(ptr[i].name, ptr[i + 1].name);
+    ptrs.add_net(pp, layers[0]);
+    for (int y = 0; y < nc; ++y) ptrs.add_net(ap[y], layers[1 + y]);
+    ptrs.add_target(u->W_targ_actor, u->b_targ_actor, layers[0]);
+    for (int y = 0; y < nc; ++y) ptrs.add_target(u->W_targ[y], u->b_targ[y], layers[1 + y]);
+    ptrs.add(atk.blob, "the target policy's blob");
+    for (int y = 0; y < nc; ++y) ptrs.add(tk[y].blob, "a target critic's blob");
+    ptrs.add(ok.blob, "the online actor's blob");
+    ptrs.add(u->critic_loss, "critic_loss");
+    ptrs.add(u->actor_loss, "actor_loss");
+    ptrs.add(u->workspace, "the workspace");
+    ptrs.add(u->target, "target");
+    ptrs.add(u->q1_next, "q1_next");
+    if (nc == 2) ptrs.add(u->q2_next, "q2_next");
+    ptrs.add(u->next_action, "next_action");
+    if (B > 0) ptrs.add_batch(*u->batch);
+    ptrs.add(u->history, "history");
+    ptrs.add(u->scale, "scale");                                         // (only read)
     const int hcols = 1 + nc;
-    if (u->history) {
-        const char *h0 = reinterpret_cast<const char *>(u->history), *h1 = h0 + (size_t)updates * hcols * sizeof(float);
-        for (int i = 0; i < np; ++i)
-            if (ptr[i].p != u->history && (const char *)ptr[i].p >= h0 && (const char *)ptr[i].p < h1)
-                return ddpg_update_fail("history", ptr[i].name);
-    }
+    if (int r = ptrs.check(fn, u->history, (size_t)updates * hcols * sizeof(float))) return r;
     if (updates == 0 || B == 0) return 0;
     // ---- the launches' arguments, once
     constexpr size_t fixed = (size_t)BLOCK * (2 * HER_DMAX + 6) * sizeof(float);
@@ -338,21 +247,9 @@ int ctr_ddpg_update(const ctr_ddpg_update_t *u, int32_t updates, void *stream)
                   "every actor and every critic fit beside the row staging");
     const size_t shm_draw = std::max(atk.bytes, std::max(tk[0].bytes, tk[1].bytes)) + ACTOR_LDS_SLACK;
     size_t shm_critic = 0;
-    for (int y = 0; y < nc; ++y) {
-        gk[y].rows = u->batch->obs;
-        gk[y].actions = u->batch->action;
-        gk[y].scale = u->scale;
-        gk[y].target = u->target;
-        gk[y].B = (int32_t)B;
-        gk[y].dq = (float)(2.0 / (double)B);
-        gk[y].beta1 = ap[y].beta1;
-        gk[y].beta2 = ap[y].beta2;
-        gk[y].pow = ap[y].pow;
-        gk[y].ws = const_cast<char *>(ap[y].ws);
-        ap[y].loss_scale = 1.0 / (double)B;
-        ap[y].loss = u->critic_loss ? u->critic_loss + y : nullptr;
-        shm_critic = std::max(shm_critic, ddpg_lds_floats(gk[y].net) * sizeof(float) + ACTOR_LDS_SLACK);
-    }
+    for (int y = 0; y < nc; ++y)
+        shm_critic = std::max(shm_critic, ddpg_critic_fill(gk[y], ap[y], u->batch->obs, u->batch->action, u->scale, u->target, B,
+                                                           u->critic_loss ? u->critic_loss + y : nullptr));
     const size_t shm_actor = (ddpg_lds_floats(pg.net) + ddpg_lds_floats(pg.crit)) * sizeof(float) + ACTOR_LDS_SLACK;
     if (nc == 1) {
         if (int r = allow_dynamic_lds(k_her_sample_td, shm_draw)) return r;
@@ -365,40 +262,21 @@ int ctr_ddpg_update(const ctr_ddpg_update_t *u, int32_t updates, void *stream)
     pg.rows = u->batch->obs;
     pg.B = (int32_t)B;
     pg.dq = (float)(-1.0 / (double)B);
-    pg.beta1 = pp.beta1;
-    pg.beta2 = pp.beta2;
-    pg.pow = pp.pow;
-    pg.ws = const_cast<char *>(pp.ws);
+    ddpg_grad_state(pg, pp);
     pp.loss_scale = -1.0 / (double)B;
     pp.loss = u->actor_loss;
     const TdK td1 = {u->gamma, u->target, u->q1_next, u->next_action};
     const Td3K td2 = {u->gamma, u->sigma, u->clip, u->target, u->q1_next, u->q2_next, u->next_action};
-    DdpgTailK ct[2] = {}, pt = {};
-    for (int y = 0; y < nc; ++y) {
-        ct[y].ap = ap[y];
-        ct[y].ak = tk[y];
-        for (int l = 0; l < layers[1 + y]; ++l) {
-            ct[y].Wt[l] = u->W_targ[y][l];
-            ct[y].bt[l] = u->b_targ[y][l];
-        }
-        ct[y].tau = u->tau;
-    }
-    pt.ap = pp;
-    pt.ak = atk;
-    for (int l = 0; l < layers[0]; ++l) {
-        pt.Wt[l] = u->W_targ_actor[l];
-        pt.bt[l] = u->b_targ_actor[l];
-    }
-    pt.tau = u->tau;
-    pt.online_blob = const_cast<void *>(ok.blob);
+    DdpgTailK ct[2] = {};
+    for (int y = 0; y < nc; ++y) ct[y].t = update_tail(ap[y], tk[y], u->W_targ[y], u->b_targ[y], layers[1 + y], u->tau);
+    DdpgTailK pt = {update_tail(pp, atk, u->W_targ_actor, u->b_targ_actor, layers[0], u->tau), const_cast<void *>(ok.blob)};
     const unsigned gc = grid_for(std::max(tk[0].bytes, tk[1].bytes) / 16), gp = grid_for(atk.bytes / 16);
     const unsigned ga = grid_for(std::max(ap[0].params, ap[1].params));
     const unsigned slots = (unsigned)ap[0].slots;
     const hipStream_t s = (hipStream_t)stream;
     const HerK hk = {*her};
     // the prefix sums of the stored rows, once: nothing below writes the store
-    hipLaunchKernelGGL(k_her_scan_tiles, dim3((unsigned)tiles), dim3(BLOCK), 0, s, hk);
-    hipLaunchKernelGGL(k_her_scan_tops, dim3(1), dim3(BLOCK), 0, s, hk, tiles);
+    her_scan(her, tiles, stream);
     bool copy_last = false;
     for (int32_t i = 0; i < updates; ++i) {
         float *hist = u->history ? u->history + (size_t)hcols * (size_t)i : nullptr;
@@ -414,9 +292,9 @@ int ctr_ddpg_update(const ctr_ddpg_update_t *u, int32_t updates, void *stream)
             hipLaunchKernelGGL(k_td3_grad, dim3(slots, 2), dim3(BLOCK), shm_critic, s, gk[0], gk[1]);
         }
         if (step) {
-            ct[0].hist = hist;
-            ct[1].hist = hist ? hist + 1 : nullptr;
-            pt.hist = hist ? hist + nc : nullptr;
+            ct[0].t.hist = hist;
+            ct[1].t.hist = hist ? hist + 1 : nullptr;
+            pt.t.hist = hist ? hist + nc : nullptr;
             hipLaunchKernelGGL(k_ddpg_critic_tail, dim3(gc, (unsigned)nc), dim3(BLOCK), 0, s, ct[0], ct[1]);
             hipLaunchKernelGGL(k_ddpg_grad<true>, dim3((unsigned)pp.slots), dim3(BLOCK), shm_actor, s, pg);
             hipLaunchKernelGGL(k_ddpg_actor_tail, dim3(gp), dim3(BLOCK), 0, s, pt);

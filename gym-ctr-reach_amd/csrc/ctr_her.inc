@@ -15,6 +15,13 @@
 // env (record / open), one lane per sampled row (sample); HBM-bound gathers and scatters.
 namespace {
 
+// The sampler's prefix sums over the store's slots (her->cdf): the two launches every draw starts with.
+void her_scan(const ctr_her_t *her, int64_t tiles, void *stream)
+{
+    hipLaunchKernelGGL(k_her_scan_tiles, dim3((unsigned)tiles), dim3(BLOCK), 0, (hipStream_t)stream, HerK{*her});
+    hipLaunchKernelGGL(k_her_scan_tops, dim3(1), dim3(BLOCK), 0, (hipStream_t)stream, HerK{*her}, tiles);
+}
+
 int check_her(const ctr_her_t *her, const char *who)
 {
     if (!her) return fail(CTR_EINVAL, who);
@@ -94,8 +101,7 @@ int ctr_her_sample(const ctr_her_t *her, int64_t batch_size, uint64_t seed, uint
     const int64_t E = her->n * her->slots;
     const int64_t tiles = (E + HER_TILE - 1) / HER_TILE;
     if (tiles > 0x7fffffff) return fail(CTR_EINVAL, "ctr_her_sample: store too large");
-    hipLaunchKernelGGL(k_her_scan_tiles, dim3((unsigned)tiles), dim3(BLOCK), 0, (hipStream_t)stream, HerK{*her});
-    hipLaunchKernelGGL(k_her_scan_tops, dim3(1), dim3(BLOCK), 0, (hipStream_t)stream, HerK{*her}, tiles);
+    her_scan(her, tiles, stream);
     hipLaunchKernelGGL(k_her_sample, dim3(grid_for(batch_size)), dim3(BLOCK), 0, (hipStream_t)stream, HerK{*her},
                        batch_size, seed, counter, o);
     return hip_check("ctr_her_sample launch");

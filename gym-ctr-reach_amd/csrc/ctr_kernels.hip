@@ -3250,5 +3250,6 @@ int ctr_follow(const ctr_env_config_t *cfg, const ctr_batch_t *batch, const ctr_
 #include "ctr_polyak.inc"
 #include "ctr_ddpg.inc"
 #include "ctr_sac.inc"
+#include "ctr_update_common.inc"
 #include "ctr_sac_update.inc"
 #include "ctr_ddpg_update.inc"

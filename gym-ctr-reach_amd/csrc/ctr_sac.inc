@@ -371,8 +371,7 @@ int ctr_her_sample_sac(const ctr_her_t *her, int64_t batch_size, uint64_t seed, 
     const size_t shm = std::max(ak.bytes, std::max(ck1.bytes, ck2.bytes)) + ACTOR_LDS_SLACK;
     if (int r = allow_dynamic_lds(k_her_sample_sac, shm)) return r;
     const HerSacK tk = {td->gamma, td->log_alpha, td->target, td->q1_next, td->q2_next, td->next_action, td->next_logp};
-    hipLaunchKernelGGL(k_her_scan_tiles, dim3((unsigned)tiles), dim3(BLOCK), 0, (hipStream_t)stream, HerK{*her});
-    hipLaunchKernelGGL(k_her_scan_tops, dim3(1), dim3(BLOCK), 0, (hipStream_t)stream, HerK{*her}, tiles);
+    her_scan(her, tiles, stream);
     hipLaunchKernelGGL(k_her_sample_sac, dim3(grid_for(batch_size)), dim3(BLOCK), shm, (hipStream_t)stream, HerK{*her},
                        batch_size, seed, counter, *out, ak, ck1, ck2, tk);
     return hip_check("ctr_her_sample_sac launch");

@@ -140,12 +140,15 @@ class _Net(object):
         self.pow.copy_(state["pow"])
 
 
-def _run_check(self, critics, her, actor_targ, targets, batch_size, gamma, tau, updates, actor, history, sigma, clip,
-               policy_delay):
-    """``DdpgLearner.update``'s and ``Td3Learner.update``'s checks (``sample_td``'s or ``sample_td3``'s,
-    ``critic_step``'s, ``polyak_``'s and ``load_``'s), before anything is allocated, converted or written.
-    ``critics``: the learner's critic ``_Net``s.  -> (B, updates, gamma, tau, sigma, clip, policy_delay,
-    [(net, target layers), ...])."""
+def _update_check(self, critics, her, policy, targets, batch_size, gamma, tau, updates, history, *, policy_cls, policy_msg,
+                  policy_name, paired, shape, two, cols, actor=None, noise=None):
+    """The three ``update`` methods' checks (the sampler's, ``critic_step``'s, ``polyak_``'s and ``load_``'s), before
+    anything is allocated, converted or written.  ``critics``: the learner's critic ``_Net``s; ``policy``: the net
+    the draw acts with, a ``policy_cls`` (``policy_msg``, ``policy_name``: its words in the messages); ``paired``:
+    it is a target, ``targets[0]``'s net (DDPG, TD3), else the online policy (SAC: its blob is refreshed from
+    the masters); ``shape``: what ``targets`` is; ``two``: the two critic targets' words; ``cols``: ``history``'s
+    width; ``actor``: DDPG's and TD3's online actor; ``noise``: their (sigma, clip, policy_delay).
+    -> (B, updates, gamma, tau, noise, [(net, target layers), ...])."""
     import torch
     from .policy import MlpActor, MlpCritic
     dev = self.device
@@ -157,23 +160,26 @@ def _run_check(self, critics, her, actor_targ, targets, batch_size, gamma, tau, 
     hdev = her.venv.device
     if elsewhere(hdev):
         raise ValueError("update: the buffer is on %s, the learner on %s" % (hdev, dev))
-    shape = "[(actor_targ, policy_targ), (critic_targ_dev, critic_targ)]" if nc == 1 else \
-        "[(actor_targ, policy_targ), (critic1_targ_dev, critic1_targ), (critic2_targ_dev, critic2_targ)]"
+    if not paired and not isinstance(policy, policy_cls):
+        raise ValueError(policy_msg % type(policy).__name__)
     targets = [tuple(t) for t in targets]
-    if len(targets) != 1 + nc or any(len(t) != 2 for t in targets):
+    first = 1 if paired else 0
+    if len(targets) != first + nc or any(len(t) != 2 for t in targets):
         raise ValueError("update: targets is " + shape)
-    if not isinstance(actor_targ, MlpActor):
-        raise ValueError("update: actor_targ must be an MlpActor, not %s" % type(actor_targ).__name__)
-    if targets[0][0] is not actor_targ:
-        raise ValueError("update: targets[0] is (actor_targ, policy_targ): its net is not actor_targ")
-    for m, (net, _) in enumerate(targets[1:]):
+    if paired:
+        if not isinstance(policy, policy_cls):
+            raise ValueError(policy_msg % type(policy).__name__)
+        if targets[0][0] is not policy:
+            raise ValueError("update: targets[0] is (actor_targ, policy_targ): its net is not actor_targ")
+    critic_targets = targets[first:]
+    for m, (net, _) in enumerate(critic_targets):
         if not isinstance(net, MlpCritic):
             raise ValueError("update: target %d must be an MlpCritic, not %s" % (m + 1, type(net).__name__))
     if actor is not None and not isinstance(actor, MlpActor):
         raise ValueError("update: actor must be an MlpActor or None, not %s" % type(actor).__name__)
-    if actor is actor_targ:
+    if actor is policy:
         raise ValueError("update: actor and actor_targ are one MlpActor: each has its own blob")
-    named = [(actor_targ, "target policy")] + [(net, "target %d" % (m + 1)) for m, (net, _) in enumerate(targets[1:])]
+    named = [(policy, policy_name)] + [(net, "target %d" % (m + 1)) for m, (net, _) in enumerate(critic_targets)]
     if actor is not None:
         named.append((actor, "actor"))
     for net, name in named:
@@ -181,22 +187,24 @@ def _run_check(self, critics, her, actor_targ, targets, batch_size, gamma, tau, 
             raise ValueError("update: the %s must be on the device" % name)
         if elsewhere(net.device):
             raise ValueError("update: the %s is on %s, the learner on %s" % (name, net.device, dev))
-    if nc == 2 and targets[1][0] is targets[2][0]:
-        raise ValueError("update: the two critic targets are one MlpCritic: each has its own blob")
+    if nc == 2 and critic_targets[0][0] is critic_targets[1][0]:
+        raise ValueError("update: the two %s are one MlpCritic: each has its own blob" % two)
     gamma, tau = float(gamma), float(tau)
     if not np.isfinite(gamma):
         raise ValueError("update: gamma must be finite")
     if not 0.0 <= tau <= 1.0:
         raise ValueError("update: tau must be in [0, 1]")
-    sigma, clip = float(sigma), float(clip)
-    if nc == 2:
-        if not (np.isfinite(sigma) and sigma >= 0.0):
-            raise ValueError("update: sigma must be finite and >= 0")
-        if not clip >= 0.0:
-            raise ValueError("update: clip must be >= 0 (inf: the noise is not clipped)")
-    policy_delay = int(policy_delay)
-    if policy_delay < 1:
-        raise ValueError("update: policy_delay must be >= 1")
+    if noise is not None:
+        sigma, clip = float(noise[0]), float(noise[1])
+        if nc == 2:
+            if not (np.isfinite(sigma) and sigma >= 0.0):
+                raise ValueError("update: sigma must be finite and >= 0")
+            if not clip >= 0.0:
+                raise ValueError("update: clip must be >= 0 (inf: the noise is not clipped)")
+        policy_delay = int(noise[2])
+        if policy_delay < 1:
+            raise ValueError("update: policy_delay must be >= 1")
+        noise = (sigma, clip, policy_delay)
     B, updates = int(batch_size), int(updates)
     if not 0 <= B <= self.max_batch:
         raise ValueError("update: batch_size = %d, the learner was built for max_batch = %d" % (B, self.max_batch))
@@ -205,92 +213,210 @@ def _run_check(self, critics, her, actor_targ, targets, batch_size, gamma, tau, 
     if her.obs_dim + 6 != self.in_dim:
         raise ValueError("update: the buffer's rows are %d floats, the policy's %d" % (her.obs_dim + 6, self.in_dim))
     done = []
-    actor_targ._device_layers(self._actor.params, "update: target policy: online ")
-    done.append((actor_targ, actor_targ._device_layers(targets[0][1], "update: target policy: target ", target=True)))
-    for m, (net, target) in enumerate(targets[1:]):
+    if paired:
+        policy._device_layers(self._actor.params, "update: target policy: online ")
+        done.append((policy, policy._device_layers(targets[0][1], "update: target policy: target ", target=True)))
+    else:
+        policy._device_layers(self._actor.params, "update: the policy's ")        # load_'s: it has the masters' shape
+    for m, (net, target) in enumerate(critic_targets):
         net._device_layers(critics[m].params, "update: target %d: online " % (m + 1))
         done.append((net, net._device_layers(target, "update: target %d: target " % (m + 1), target=True)))
     if actor is not None:
-        actor._device_layers(self._actor.params, "update: the actor's ")        # load_'s: actor has the masters' shape
+        actor._device_layers(self._actor.params, "update: the actor's ")          # load_'s
     if history is not None:
         if not (isinstance(history, torch.Tensor) and history.dtype == torch.float32 and not elsewhere(history.device)
-                and tuple(history.shape) == (updates, 1 + nc) and history.is_contiguous()):
+                and tuple(history.shape) == (updates, cols) and history.is_contiguous()):
             raise ValueError("update: history must be a contiguous float32 [updates, %d] = [%d, %d] tensor on %s"
-                             % (1 + nc, updates, 1 + nc, dev))
-    return B, updates, gamma, tau, sigma, clip, policy_delay, done
+                             % (cols, updates, cols, dev))
+    return B, updates, gamma, tau, noise, done
+
+
+def _cache_slot(self, key):
+    """-> (the learner's cache of update structs, its entry for ``key`` or None: eight entries, emptied
+    before a ninth)."""
+    cache = self.__dict__.setdefault("_update_cache", {})
+    entry = cache.get(key)
+    if entry is None and len(cache) >= 8:
+        cache.clear()
+    return cache, entry
+
+
+def _update_struct(self, u, her, B, extra):
+    """What a new ``ctr_sac_update_t`` or ``ctr_ddpg_update_t`` ``u`` takes from the buffer and the learner:
+    the batch's output tensors (with the target and those named in ``extra``), the policy's and the
+    critics' learning state, the scale, the losses, the workspace -> (the batch dict, its ctr_her_batch_t)."""
+    import torch
+    _, out, hb = her._batch(B, False)
+    for name in ("target",) + tuple(extra):
+        out[name] = torch.empty((B, 6) if name == "next_action" else B, dtype=torch.float32, device=self.device)
+    u.her, u.batch_size, u.draw_seed, u.batch = ctypes.pointer(her._h), B, her._draw_seed(None), ctypes.pointer(hb)
+    u.target, u.next_action = _abi.ptr(out["target"]), _abi.ptr(out.get("next_action"))
+    u.policy_net, u.policy_adam = ctypes.pointer(self._actor.struct), ctypes.pointer(self._actor.adam)
+    u.scale = self._scale_p
+    u.critic_loss, u.actor_loss = self._closs, self._aloss
+    u.workspace, u.workspace_bytes = self._ws, self._ws_bytes
+    return out, hb
+
+
+def _update_critic(u, y, struct, critic, net, tg):
+    """Critic ``y`` of an update struct: its shape, its ``_Net``, its target ``net`` and the target's layers
+    ``tg`` -> the two pointer arrays, which the caller keeps alive."""
+    W = (_abi._P * len(tg))(*[w.data_ptr() for w, _ in tg])
+    b = (_abi._P * len(tg))(*[v.data_ptr() for _, v in tg])
+    u.critic[y], u.critic_net[y] = ctypes.pointer(struct), ctypes.pointer(critic.struct)
+    u.critic_targ[y], u.W_targ[y], u.b_targ[y] = ctypes.pointer(net._struct), W, b
+    if y == 0:
+        u.critic_adam = ctypes.pointer(critic.adam)
+    return [W, b]
+
+
+def _update_call(self, fn, name, u, updates, history, stream):
+    """The C call ``fn`` (``name``) of ``updates`` updates on the current stream (or ``stream``)."""
+    u.history = None if history is None else history.data_ptr()
+    s = stream.cuda_stream if stream is not None else self._raw_stream(self._index)
+    rc = fn(u, updates, s)
+    if rc:
+        _abi.check(rc, name)
+
+
+def _refreshed(net, sources):
+    """A net as ``load_`` / ``polyak_`` leave it: sources set, host copies dropped."""
+    net._sources = sources
+    net.weights = net.biases = net.packed = None
 
 
 def _run_update(self, critic_structs, critics, her, actor_targ, targets, batch_size, gamma, tau, updates, actor, history,
                 return_next, stream, sigma=0.0, clip=0.0, policy_delay=1, update_index=0):
     """The work of ``DdpgLearner.update`` and ``Td3Learner.update`` (ctr_ddpg_update) -> (the batch dict,
     updates)."""
-    import torch
     from . import _abi_ddpg
+    from .policy import MlpActor
     nc = len(critics)
-    B, updates, gamma, tau, sigma, clip, policy_delay, done = _run_check(
-        self, critics, her, actor_targ, targets, batch_size, gamma, tau, updates, actor, history, sigma, clip, policy_delay)
+    B, updates, gamma, tau, (sigma, clip, policy_delay), done = _update_check(
+        self, critics, her, actor_targ, targets, batch_size, gamma, tau, updates, history,
+        policy_cls=MlpActor, policy_msg="update: actor_targ must be an MlpActor, not %s", policy_name="target policy",
+        paired=True, two="critic targets", cols=1 + nc, actor=actor, noise=(sigma, clip, policy_delay),
+        shape="[(actor_targ, policy_targ), (critic_targ_dev, critic_targ)]" if nc == 1 else
+        "[(actor_targ, policy_targ), (critic1_targ_dev, critic1_targ), (critic2_targ_dev, critic2_targ)]")
     key = (id(her), B, bool(return_next), id(actor), None if actor is None else actor.blob.data_ptr()) + tuple(
         (id(net), net.blob.data_ptr()) + tuple(t.data_ptr() for pair in tg for t in pair) for net, tg in done)
-    cache = self.__dict__.setdefault("_update_cache", {})
-    entry = cache.get(key)
+    cache, entry = _cache_slot(self, key)
     if entry is None:
-        if len(cache) >= 8:
-            cache.clear()
-        _, out, hb = her._batch(B, False)
-        dev = self.device
-        out["target"] = torch.empty(B, dtype=torch.float32, device=dev)
-        if return_next:
-            for name in ("q_next",) if nc == 1 else ("q1_next", "q2_next"):
-                out[name] = torch.empty(B, dtype=torch.float32, device=dev)
-            out["next_action"] = torch.empty((B, 6), dtype=torch.float32, device=dev)
         u = _abi_ddpg.CtrDdpgUpdate()
-        u.her, u.batch_size, u.draw_seed, u.batch = ctypes.pointer(her._h), B, her._draw_seed(None), ctypes.pointer(hb)
-        u.target, u.next_action = _abi.ptr(out["target"]), _abi.ptr(out.get("next_action"))
-        u.q1_next, u.q2_next = _abi.ptr(out.get("q_next" if nc == 1 else "q1_next")), _abi.ptr(out.get("q2_next"))
+        q_next = ("q_next",) if nc == 1 else ("q1_next", "q2_next")
+        out, hb = _update_struct(self, u, her, B, q_next + ("next_action",) if return_next else ())
+        u.q1_next, u.q2_next = _abi.ptr(out.get(q_next[0])), _abi.ptr(out.get("q2_next"))
         u.n_critics = nc
-        u.policy, u.policy_net = ctypes.pointer(self._actor_struct), ctypes.pointer(self._actor.struct)
-        u.policy_adam, u.critic_adam = ctypes.pointer(self._actor.adam), ctypes.pointer(critics[0].adam)
-        arrays = []
-        for m, (net, tg) in enumerate(done):
-            W = (_abi._P * len(tg))(*[w.data_ptr() for w, _ in tg])
-            b = (_abi._P * len(tg))(*[v.data_ptr() for _, v in tg])
-            arrays += [W, b]
-            if m == 0:
-                u.actor_targ, u.W_targ_actor, u.b_targ_actor = ctypes.pointer(net._struct), W, b
-                continue
-            y = m - 1
-            u.critic[y] = ctypes.pointer(critic_structs[y])
-            u.critic_net[y] = ctypes.pointer(critics[y].struct)
-            u.critic_targ[y], u.W_targ[y], u.b_targ[y] = ctypes.pointer(net._struct), W, b
+        u.policy = ctypes.pointer(self._actor_struct)
+        tg = done[0][1]
+        arrays = [(_abi._P * len(tg))(*[w.data_ptr() for w, _ in tg]), (_abi._P * len(tg))(*[v.data_ptr() for _, v in tg])]
+        u.actor_targ, u.W_targ_actor, u.b_targ_actor = ctypes.pointer(actor_targ._struct), arrays[0], arrays[1]
+        for y, (net, tg) in enumerate(done[1:]):
+            arrays += _update_critic(u, y, critic_structs[y], critics[y], net, tg)
         if actor is not None:
             u.actor = ctypes.pointer(actor._struct)
-        u.scale = self._scale_p
-        u.critic_loss, u.actor_loss = self._closs, self._aloss
-        u.workspace, u.workspace_bytes = self._ws, self._ws_bytes
         # (the entry keeps alive what the struct points into, and the objects whose ids are the key)
         entry = cache[key] = (u, out, hb, arrays, her, actor, done)
     u, out = entry[0], entry[1]
     u.gamma, u.tau, u.sigma, u.clip = gamma, tau, sigma, clip
     u.policy_delay, u.update_index = policy_delay, int(update_index) & 0xFFFFFFFFFFFFFFFF
     u.draw_counter = her._counter & 0xFFFFFFFFFFFFFFFF
-    u.history = None if history is None else history.data_ptr()
-    s = stream.cuda_stream if stream is not None else self._raw_stream(self._index)
-    rc = self._lib.ctr_ddpg_update(u, updates, s)
-    if rc:
-        _abi.check(rc, "ctr_ddpg_update")
+    _update_call(self, self._lib.ctr_ddpg_update, "ctr_ddpg_update", u, updates, history, stream)
     her._counter += updates
     if B and (int(update_index) + updates) // policy_delay > int(update_index) // policy_delay:
         # a policy step was made: the nets are as polyak_ and load_ leave them
         for net, tg in done:
-            net._sources = tg
-            net.weights = net.biases = net.packed = None
+            _refreshed(net, tg)
         if actor is not None:
-            actor._sources = list(self._actor.params)
-            actor.weights = actor.biases = actor.packed = None
+            _refreshed(actor, list(self._actor.params))
     out = dict(out)
     if history is not None:
         out["history"] = history
     return out, updates
+
+
+def _setup(self, policy, tanh, out_rows, critics, scale, rates, betas, eps, max_batch, alloc, workspace_fn):
+    """The three constructors' work: the checks, the ``_Net`` of the policy and of each critic, the
+    workspace (``workspace_fn``'s bytes) and everything ``critic_step`` takes.  ``tanh``, ``out_rows``: the
+    policy's head; ``critics``: ((network, its name), ...), one (``_critic``, ``_critic_struct``,
+    ``critic_loss`` 0-d) or two (``_critics``, ``_critic_structs``, ``critic_loss`` [2], the twin step's
+    pairs); ``rates``: ((name, value), ...), every value finite, the first two the policy's and the
+    critics' learning rates."""
+    import torch
+    from . import _abi_ddpg, _abi_td3
+    a_params, a_in, a_hidden = _masters(policy, tanh, "policy", (19, 20), out_rows,
+                                        "the policy's rows are obs_dim + 6 = 19 or 20 floats")
+    c_nets = []
+    for critic, name in critics:
+        c_params, c_in, c_hidden = _masters(critic, False, name, (25, 26), 1,
+                                            "the %s's rows are obs_dim + 12 = 25 or 26 floats" % name)
+        if a_in + 6 != c_in:
+            raise ValueError("the %s takes [row, action]: %d + 6 inputs, not %d" % (name, a_in, c_in))
+        c_nets.append((c_params, c_in, c_hidden))
+    self.device = device = a_params[0][0].device
+    for (c_params, _, _), (_, name) in zip(c_nets, critics):
+        if c_params[0][0].device != device:
+            raise ValueError("the %s is on %s, the policy on %s" % (name, c_params[0][0].device, device))
+    if len(c_nets) == 2 and any(t1 is t2 or (t1.numel() and t1.data_ptr() == t2.data_ptr())
+                                for p1 in c_nets[0][0] for t1 in p1 for p2 in c_nets[1][0] for t2 in p2):
+        raise ValueError("critic1 and critic2 share a tensor: the twin step updates them side by side")
+    betas = (float(betas[0]), float(betas[1]))
+    for name, val in tuple(rates) + (("eps", eps),):
+        if not np.isfinite(float(val)):
+            raise ValueError(name + " must be finite")
+    if not all(0.0 <= b < 1.0 for b in betas):
+        raise ValueError("betas must be in [0, 1)")
+    if not float(eps) > 0.0:
+        raise ValueError("eps must be positive")
+    max_batch = int(max_batch)
+    if not 1 <= max_batch <= _abi_ddpg.CTR_DDPG_MAX_B:
+        raise ValueError("max_batch must be in 1..%d" % _abi_ddpg.CTR_DDPG_MAX_B)
+    if scale is not None:
+        scale = np.asarray(scale, dtype=np.float32).reshape(-1)
+        if scale.shape != (6,) or not np.isfinite(scale).all() or (scale == 0).any():
+            raise ValueError("scale is six finite, non-zero floats")
+    if device.type != "cuda":
+        raise ValueError("the networks are on %s: the learner's networks are on a GPU" % (device,))
+    if alloc is None:
+        def alloc(shape):
+            return torch.zeros(shape, dtype=torch.float32, device=device)
+    self._lib = lib = _abi.load()
+    self.max_batch = max_batch
+    self.in_dim = a_in
+    self._actor_struct = sa = _abi.CtrActor()
+    sc = tuple(_abi_critic.CtrCritic() for _ in c_nets)
+    for s, in_dim, hidden in [(sa, a_in, a_hidden)] + [(c,) + net[1:] for c, net in zip(sc, c_nets)]:
+        s.in_dim, s.n_hidden = in_dim, len(hidden)
+        for l, w in enumerate(hidden):
+            s.width[l] = w
+    actor_lr, critic_lr = rates[0][1], rates[1][1]
+    self._actor = _Net(a_params, alloc, actor_lr, betas, eps)
+    nets = tuple(_Net(net[0], alloc, critic_lr, betas, eps) for net in c_nets)
+    self.actor_grads = self._actor.grads
+    nbytes = int(getattr(lib, workspace_fn)(sa, *sc, max_batch))
+    if nbytes < 0:
+        raise _abi.CtrError(workspace_fn + ": " + lib.ctr_last_error().decode())
+    self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    if self.workspace.data_ptr() % 16:
+        raise RuntimeError("workspace not 16-B aligned")
+    self.scale = None if scale is None else torch.from_numpy(scale).to(device)
+    self.critic_loss = torch.zeros(() if len(nets) == 1 else 2, dtype=torch.float32, device=device)
+    self.actor_loss = torch.zeros((), dtype=torch.float32, device=device)
+    # everything the steps take but the batch and the stream, once
+    P = ctypes.c_void_p
+    if len(nets) == 1:
+        self._critic, self._critic_struct, self.critic_grads = nets[0], sc[0], nets[0].grads
+        self._critic_step = lib.ctr_ddpg_critic_step
+    else:
+        self._critics, self._critic_structs, self.critic_grads = nets, sc, (nets[0].grads, nets[1].grads)
+        self._critic_pair = _abi_td3.CriticPair(ctypes.pointer(sc[0]), ctypes.pointer(sc[1]))
+        self._net_pair = _abi_td3.NetPair(ctypes.pointer(nets[0].struct), ctypes.pointer(nets[1].struct))
+        self._critic_step = lib.ctr_td3_critic_step
+    self._ws, self._ws_bytes = P(self.workspace.data_ptr()), nbytes
+    self._scale_p = P(None if self.scale is None else self.scale.data_ptr())
+    self._closs, self._aloss = P(self.critic_loss.data_ptr()), P(self.actor_loss.data_ptr())
+    self._f32, self._index = torch.float32, device.index
+    self._raw_stream = torch._C._cuda_getCurrentRawStream
 
 
 class DdpgLearner(object):
@@ -313,66 +439,9 @@ class DdpgLearner(object):
 
     def __init__(self, policy, critic, scale=None, actor_lr=1e-4, critic_lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  max_batch=256, alloc=None):
-        import torch
-        from . import _abi_ddpg
-        a_params, a_in, a_hidden = _masters(policy, True, "policy", (19, 20), 6,
-                                            "the policy's rows are obs_dim + 6 = 19 or 20 floats")
-        c_params, c_in, c_hidden = _masters(critic, False, "critic", (25, 26), 1,
-                                            "the critic's rows are obs_dim + 12 = 25 or 26 floats")
-        if a_in + 6 != c_in:
-            raise ValueError("the critic takes [row, action]: %d + 6 inputs, not %d" % (a_in, c_in))
-        self.device = device = a_params[0][0].device
-        if c_params[0][0].device != device:
-            raise ValueError("the critic is on %s, the policy on %s" % (c_params[0][0].device, device))
-        betas = (float(betas[0]), float(betas[1]))
-        for name, val in (("actor_lr", actor_lr), ("critic_lr", critic_lr), ("eps", eps)):
-            if not np.isfinite(float(val)):
-                raise ValueError(name + " must be finite")
-        if not all(0.0 <= b < 1.0 for b in betas):
-            raise ValueError("betas must be in [0, 1)")
-        if not float(eps) > 0.0:
-            raise ValueError("eps must be positive")
-        max_batch = int(max_batch)
-        if not 1 <= max_batch <= _abi_ddpg.CTR_DDPG_MAX_B:
-            raise ValueError("max_batch must be in 1..%d" % _abi_ddpg.CTR_DDPG_MAX_B)
-        if scale is not None:
-            scale = np.asarray(scale, dtype=np.float32).reshape(-1)
-            if scale.shape != (6,) or not np.isfinite(scale).all() or (scale == 0).any():
-                raise ValueError("scale is six finite, non-zero floats")
-        if device.type != "cuda":
-            raise ValueError("the networks are on %s: the learner's networks are on a GPU" % (device,))
-        if alloc is None:
-            def alloc(shape):
-                return torch.zeros(shape, dtype=torch.float32, device=device)
-        self._lib = lib = _abi.load()
-        self.max_batch = max_batch
-        self.in_dim = a_in
-        self._actor_struct = sa = _abi.CtrActor()
-        self._critic_struct = sc = _abi_critic.CtrCritic()
-        for s, in_dim, hidden in ((sa, a_in, a_hidden), (sc, c_in, c_hidden)):
-            s.in_dim, s.n_hidden = in_dim, len(hidden)
-            for l, w in enumerate(hidden):
-                s.width[l] = w
-        self._actor = _Net(a_params, alloc, actor_lr, betas, eps)
-        self._critic = _Net(c_params, alloc, critic_lr, betas, eps)
-        self.actor_grads, self.critic_grads = self._actor.grads, self._critic.grads
-        nbytes = int(lib.ctr_ddpg_workspace_bytes(sa, sc, max_batch))
-        if nbytes < 0:
-            raise _abi.CtrError("ctr_ddpg_workspace_bytes: " + lib.ctr_last_error().decode())
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        if self.workspace.data_ptr() % 16:
-            raise RuntimeError("workspace not 16-B aligned")
-        self.scale = None if scale is None else torch.from_numpy(scale).to(device)
-        self.critic_loss = torch.zeros((), dtype=torch.float32, device=device)
-        self.actor_loss = torch.zeros((), dtype=torch.float32, device=device)
-        # everything the two calls take but the batch and the stream, once
-        P = ctypes.c_void_p
-        self._ws, self._ws_bytes = P(self.workspace.data_ptr()), nbytes
-        self._scale_p = P(None if self.scale is None else self.scale.data_ptr())
-        self._closs, self._aloss = P(self.critic_loss.data_ptr()), P(self.actor_loss.data_ptr())
-        self._critic_step, self._actor_step = lib.ctr_ddpg_critic_step, lib.ctr_ddpg_actor_step
-        self._f32, self._index = torch.float32, device.index
-        self._raw_stream = torch._C._cuda_getCurrentRawStream
+        _setup(self, policy, True, 6, ((critic, "critic"),), scale, (("actor_lr", actor_lr), ("critic_lr", critic_lr)), betas,
+               eps, max_batch, alloc, "ctr_ddpg_workspace_bytes")
+        self._actor_step = self._lib.ctr_ddpg_actor_step
 
     def _rows(self, t, cols, name):
         if t.dtype is not self._f32 or t.device != self.device or t.dim() != 2 or t.shape[1] != cols \
@@ -383,16 +452,21 @@ class DdpgLearner(object):
             raise ValueError("B = %d rows, the learner was built for max_batch = %d" % (B, self.max_batch))
         return B
 
-    def critic_step(self, rows, actions, target, stream=None):
-        """One regression step of the critic on ``target`` ([B] float32): rows [B, in_dim] as the
-        policy takes them, actions [B, 6] (divided by ``scale`` in the kernel when the learner has
-        one).  The loss goes to ``critic_loss``, the gradients to ``critic_grads``."""
+    def _critic_batch(self, rows, actions, target):
+        """``critic_step``'s checks of its batch -> B."""
         B = self._rows(rows, self.in_dim, "rows")
         if self._rows(actions, 6, "actions") != B:
             raise ValueError("actions has another B than rows")
         if target.dtype is not self._f32 or target.device != self.device or tuple(target.shape) != (B,) \
                 or not target.is_contiguous():
             raise ValueError("target must be a contiguous float32 [B] tensor on %s" % (self.device,))
+        return B
+
+    def critic_step(self, rows, actions, target, stream=None):
+        """One regression step of the critic on ``target`` ([B] float32): rows [B, in_dim] as the
+        policy takes them, actions [B, 6] (divided by ``scale`` in the kernel when the learner has
+        one).  The loss goes to ``critic_loss``, the gradients to ``critic_grads``."""
+        B = self._critic_batch(rows, actions, target)
         s = stream.cuda_stream if stream is not None else self._raw_stream(self._index)
         c = self._critic
         rc = self._critic_step(self._critic_struct, c.struct, c.adam, rows.data_ptr(), actions.data_ptr(), self._scale_p,
@@ -475,100 +549,18 @@ class Td3Learner(object):
 
     def __init__(self, policy, critic1, critic2, scale=None, actor_lr=1e-4, critic_lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  max_batch=256, alloc=None):
-        self._setup(policy, True, 6, critic1, critic2, scale, (("actor_lr", actor_lr), ("critic_lr", critic_lr)), betas, eps,
-                    max_batch, alloc, "ctr_td3_workspace_bytes")
+        _setup(self, policy, True, 6, ((critic1, "critic1"), (critic2, "critic2")), scale,
+               (("actor_lr", actor_lr), ("critic_lr", critic_lr)), betas, eps, max_batch, alloc, "ctr_td3_workspace_bytes")
         self._actor_step = self._lib.ctr_ddpg_actor_step
         self.update_count = 0           # the updates made through ``update``: where TD3's delayed steps fall
 
-    def _setup(self, policy, tanh, out_rows, critic1, critic2, scale, rates, betas, eps, max_batch, alloc, workspace_fn):
-        """The constructor's work, which ``SacLearner`` shares: the checks, the three ``_Net``, the
-        workspace (``workspace_fn``'s bytes) and everything ``critic_step`` takes.  ``tanh``,
-        ``out_rows``: the policy's head; ``rates``: ((name, value), ...), every value finite, the
-        first two the policy's and the critics' learning rates."""
-        import torch
-        from . import _abi_ddpg, _abi_td3
-        a_params, a_in, a_hidden = _masters(policy, tanh, "policy", (19, 20), out_rows,
-                                            "the policy's rows are obs_dim + 6 = 19 or 20 floats")
-        c_nets = []
-        for critic, name in ((critic1, "critic1"), (critic2, "critic2")):
-            c_params, c_in, c_hidden = _masters(critic, False, name, (25, 26), 1,
-                                                "the %s's rows are obs_dim + 12 = 25 or 26 floats" % name)
-            if a_in + 6 != c_in:
-                raise ValueError("the %s takes [row, action]: %d + 6 inputs, not %d" % (name, a_in, c_in))
-            c_nets.append((c_params, c_in, c_hidden))
-        self.device = device = a_params[0][0].device
-        for (c_params, _, _), name in zip(c_nets, ("critic1", "critic2")):
-            if c_params[0][0].device != device:
-                raise ValueError("the %s is on %s, the policy on %s" % (name, c_params[0][0].device, device))
-        if any(t1 is t2 or (t1.numel() and t1.data_ptr() == t2.data_ptr())
-               for p1 in c_nets[0][0] for t1 in p1 for p2 in c_nets[1][0] for t2 in p2):
-            raise ValueError("critic1 and critic2 share a tensor: the twin step updates them side by side")
-        betas = (float(betas[0]), float(betas[1]))
-        for name, val in tuple(rates) + (("eps", eps),):
-            if not np.isfinite(float(val)):
-                raise ValueError(name + " must be finite")
-        if not all(0.0 <= b < 1.0 for b in betas):
-            raise ValueError("betas must be in [0, 1)")
-        if not float(eps) > 0.0:
-            raise ValueError("eps must be positive")
-        max_batch = int(max_batch)
-        if not 1 <= max_batch <= _abi_ddpg.CTR_DDPG_MAX_B:
-            raise ValueError("max_batch must be in 1..%d" % _abi_ddpg.CTR_DDPG_MAX_B)
-        if scale is not None:
-            scale = np.asarray(scale, dtype=np.float32).reshape(-1)
-            if scale.shape != (6,) or not np.isfinite(scale).all() or (scale == 0).any():
-                raise ValueError("scale is six finite, non-zero floats")
-        if device.type != "cuda":
-            raise ValueError("the networks are on %s: the learner's networks are on a GPU" % (device,))
-        if alloc is None:
-            def alloc(shape):
-                return torch.zeros(shape, dtype=torch.float32, device=device)
-        self._lib = lib = _abi.load()
-        self.max_batch = max_batch
-        self.in_dim = a_in
-        self._actor_struct = sa = _abi.CtrActor()
-        self._critic_structs = sc = (_abi_critic.CtrCritic(), _abi_critic.CtrCritic())
-        for s, in_dim, hidden in ((sa, a_in, a_hidden), (sc[0],) + c_nets[0][1:], (sc[1],) + c_nets[1][1:]):
-            s.in_dim, s.n_hidden = in_dim, len(hidden)
-            for l, w in enumerate(hidden):
-                s.width[l] = w
-        actor_lr, critic_lr = rates[0][1], rates[1][1]
-        self._actor = _Net(a_params, alloc, actor_lr, betas, eps)
-        self._critics = (_Net(c_nets[0][0], alloc, critic_lr, betas, eps), _Net(c_nets[1][0], alloc, critic_lr, betas, eps))
-        self.actor_grads = self._actor.grads
-        self.critic_grads = (self._critics[0].grads, self._critics[1].grads)
-        nbytes = int(getattr(lib, workspace_fn)(sa, sc[0], sc[1], max_batch))
-        if nbytes < 0:
-            raise _abi.CtrError(workspace_fn + ": " + lib.ctr_last_error().decode())
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        if self.workspace.data_ptr() % 16:
-            raise RuntimeError("workspace not 16-B aligned")
-        self.scale = None if scale is None else torch.from_numpy(scale).to(device)
-        self.critic_loss = torch.zeros(2, dtype=torch.float32, device=device)
-        self.actor_loss = torch.zeros((), dtype=torch.float32, device=device)
-        # everything the two calls take but the batch and the stream, once
-        P = ctypes.c_void_p
-        self._critic_pair = _abi_td3.CriticPair(ctypes.pointer(sc[0]), ctypes.pointer(sc[1]))
-        self._net_pair = _abi_td3.NetPair(ctypes.pointer(self._critics[0].struct), ctypes.pointer(self._critics[1].struct))
-        self._ws, self._ws_bytes = P(self.workspace.data_ptr()), nbytes
-        self._scale_p = P(None if self.scale is None else self.scale.data_ptr())
-        self._closs, self._aloss = P(self.critic_loss.data_ptr()), P(self.actor_loss.data_ptr())
-        self._critic_step = lib.ctr_td3_critic_step
-        self._f32, self._index = torch.float32, device.index
-        self._raw_stream = torch._C._cuda_getCurrentRawStream
-
-    _rows = DdpgLearner._rows
+    _rows, _critic_batch = DdpgLearner._rows, DdpgLearner._critic_batch
 
     def critic_step(self, rows, actions, target, stream=None):
         """One regression step of both critics on ``target`` ([B] float32), as
         ``DdpgLearner.critic_step`` makes it for one.  The losses go to ``critic_loss`` [2], the
         gradients to ``critic_grads``."""
-        B = self._rows(rows, self.in_dim, "rows")
-        if self._rows(actions, 6, "actions") != B:
-            raise ValueError("actions has another B than rows")
-        if target.dtype is not self._f32 or target.device != self.device or tuple(target.shape) != (B,) \
-                or not target.is_contiguous():
-            raise ValueError("target must be a contiguous float32 [B] tensor on %s" % (self.device,))
+        B = self._critic_batch(rows, actions, target)
         s = stream.cuda_stream if stream is not None else self._raw_stream(self._index)
         rc = self._critic_step(self._critic_pair, self._net_pair, self._critics[0].adam, rows.data_ptr(),
                                actions.data_ptr(), self._scale_p, target.data_ptr(), B, self._closs, self._ws,
@@ -654,9 +646,9 @@ class SacLearner(object):
         from . import _abi_sac
         if not (np.isfinite(float(init_alpha)) and float(init_alpha) > 0.0):
             raise ValueError("init_alpha must be positive and finite")
-        self._setup(policy, False, 12, critic1, critic2, scale,
-                    (("actor_lr", actor_lr), ("critic_lr", critic_lr), ("alpha_lr", alpha_lr), ("target_entropy", target_entropy)),
-                    betas, eps, max_batch, alloc, "ctr_sac_workspace_bytes")
+        _setup(self, policy, False, 12, ((critic1, "critic1"), (critic2, "critic2")), scale,
+               (("actor_lr", actor_lr), ("critic_lr", critic_lr), ("alpha_lr", alpha_lr), ("target_entropy", target_entropy)),
+               betas, eps, max_batch, alloc, "ctr_sac_workspace_bytes")
         device = self.device
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.counter = 0
@@ -674,8 +666,7 @@ class SacLearner(object):
         self._lpm, self._la = P(self.logp_mean.data_ptr()), P(self.log_alpha.data_ptr())
         self._actor_step = self._lib.ctr_sac_actor_step
 
-    _rows = DdpgLearner._rows
-    _setup = Td3Learner._setup
+    _rows, _critic_batch = DdpgLearner._rows, DdpgLearner._critic_batch
     critic_step = Td3Learner.critic_step
 
     @property
@@ -700,59 +691,6 @@ class SacLearner(object):
                               self._aloss, self._lpm, self._ws, self._ws_bytes, s)
         if rc:
             _abi.check(rc, "ctr_sac_actor_step")
-
-    def _update_check(self, her, pi, targets, batch_size, gamma, tau, updates, history):
-        """``update``'s checks (``sample_sac``'s, ``critic_step``'s, ``load_``'s and ``polyak_``'s), before
-        anything is allocated, converted or written -> (B, updates, gamma, tau, [(net, target layers), ...])."""
-        import torch
-        from .policy import GaussianActor, MlpCritic
-        dev = self.device
-
-        def elsewhere(d):
-            return d.type != dev.type or (None not in (d.index, dev.index) and d.index != dev.index)
-
-        hdev = her.venv.device
-        if elsewhere(hdev):
-            raise ValueError("update: the buffer is on %s, the learner on %s" % (hdev, dev))
-        if not isinstance(pi, GaussianActor):
-            raise ValueError("update: pi must be a GaussianActor (the 12-row head), not %s" % type(pi).__name__)
-        targets = [tuple(t) for t in targets]
-        if len(targets) != 2 or any(len(t) != 2 for t in targets):
-            raise ValueError("update: targets is [(critic1_targ_dev, critic1_targ), (critic2_targ_dev, critic2_targ)]")
-        for m, (net, _) in enumerate(targets):
-            if not isinstance(net, MlpCritic):
-                raise ValueError("update: target %d must be an MlpCritic, not %s" % (m + 1, type(net).__name__))
-        for net, name in ((pi, "policy"), (targets[0][0], "target 1"), (targets[1][0], "target 2")):
-            if getattr(net, "blob", None) is None:
-                raise ValueError("update: the %s must be on the device" % name)
-            if elsewhere(net.device):
-                raise ValueError("update: the %s is on %s, the learner on %s" % (name, net.device, dev))
-        if targets[0][0] is targets[1][0]:
-            raise ValueError("update: the two targets are one MlpCritic: each has its own blob")
-        gamma, tau = float(gamma), float(tau)
-        if not np.isfinite(gamma):
-            raise ValueError("update: gamma must be finite")
-        if not 0.0 <= tau <= 1.0:
-            raise ValueError("update: tau must be in [0, 1]")
-        B, updates = int(batch_size), int(updates)
-        if not 0 <= B <= self.max_batch:
-            raise ValueError("update: batch_size = %d, the learner was built for max_batch = %d" % (B, self.max_batch))
-        if updates < 0:
-            raise ValueError("update: updates must be >= 0")
-        if her.obs_dim + 6 != self.in_dim:
-            raise ValueError("update: the buffer's rows are %d floats, the policy's %d" % (her.obs_dim + 6, self.in_dim))
-        pi._device_layers(self._actor.params, "update: the policy's ")            # load_'s: pi has the masters' shape
-        done = []
-        for m, (net, target) in enumerate(targets):
-            net._device_layers(self._critics[m].params, "update: target %d: online " % (m + 1))
-            tg = net._device_layers(target, "update: target %d: target " % (m + 1), target=True)
-            done.append((net, tg))
-        if history is not None:
-            if not (isinstance(history, torch.Tensor) and history.dtype == torch.float32 and not elsewhere(history.device)
-                    and tuple(history.shape) == (updates, 5) and history.is_contiguous()):
-                raise ValueError("update: history must be a contiguous float32 [updates, 5] = [%d, 5] tensor on %s"
-                                 % (updates, dev))
-        return B, updates, gamma, tau, done
 
     def update(self, her, pi, targets, batch_size, gamma, tau, updates=1, history=None, return_next=False, stream=None):
         """``updates`` whole SAC updates from one call (ctr_sac_update): each is what
@@ -785,43 +723,26 @@ class SacLearner(object):
         no allocation after the first call, no host read; a captured call repeats its draws on replay
         (the counters are arguments).  The call's struct is built once per (her, pi, targets,
         batch_size) and cached."""
-        import torch
         from . import _abi_sac
-        B, updates, gamma, tau, done = self._update_check(her, pi, targets, batch_size, gamma, tau, updates, history)
+        from .policy import GaussianActor
+        B, updates, gamma, tau, _, done = _update_check(
+            self, self._critics, her, pi, targets, batch_size, gamma, tau, updates, history,
+            policy_cls=GaussianActor, policy_msg="update: pi must be a GaussianActor (the 12-row head), not %s",
+            policy_name="policy", paired=False, two="targets", cols=5,
+            shape="[(critic1_targ_dev, critic1_targ), (critic2_targ_dev, critic2_targ)]")
         key = (id(her), id(pi), B, bool(return_next), pi.blob.data_ptr()) + tuple(
             (id(net), net.blob.data_ptr()) + tuple(t.data_ptr() for pair in tg for t in pair) for net, tg in done)
-        cache = self.__dict__.setdefault("_update_cache", {})
-        entry = cache.get(key)
+        cache, entry = _cache_slot(self, key)
         if entry is None:
-            if len(cache) >= 8:
-                cache.clear()
-            _, out, hb = her._batch(B, False)
-            dev = self.device
-            out["target"] = torch.empty(B, dtype=torch.float32, device=dev)
-            if return_next:
-                out["q1_next"] = torch.empty(B, dtype=torch.float32, device=dev)
-                out["q2_next"] = torch.empty(B, dtype=torch.float32, device=dev)
-                out["next_action"] = torch.empty((B, 6), dtype=torch.float32, device=dev)
-                out["next_logp"] = torch.empty(B, dtype=torch.float32, device=dev)
             u = _abi_sac.CtrSacUpdate()
-            u.her, u.batch_size, u.draw_seed, u.batch = ctypes.pointer(her._h), B, her._draw_seed(None), ctypes.pointer(hb)
-            u.target, u.q1_next, u.q2_next = _abi.ptr(out["target"]), _abi.ptr(out.get("q1_next")), _abi.ptr(out.get("q2_next"))
-            u.next_action, u.next_logp = _abi.ptr(out.get("next_action")), _abi.ptr(out.get("next_logp"))
-            u.policy, u.policy_net = ctypes.pointer(pi._struct), ctypes.pointer(self._actor.struct)
-            u.policy_adam, u.critic_adam = ctypes.pointer(self._actor.adam), ctypes.pointer(self._critics[0].adam)
+            out, hb = _update_struct(self, u, her, B, ("q1_next", "q2_next", "next_action", "next_logp") if return_next else ())
+            u.q1_next, u.q2_next = _abi.ptr(out.get("q1_next")), _abi.ptr(out.get("q2_next"))
+            u.next_logp = _abi.ptr(out.get("next_logp"))
+            u.policy = ctypes.pointer(pi._struct)
             arrays = []
             for y, (net, tg) in enumerate(done):
-                u.critic[y] = ctypes.pointer(self._critic_structs[y])
-                u.critic_net[y] = ctypes.pointer(self._critics[y].struct)
-                u.critic_targ[y] = ctypes.pointer(net._struct)
-                W = (_abi._P * len(tg))(*[w.data_ptr() for w, _ in tg])
-                b = (_abi._P * len(tg))(*[v.data_ptr() for _, v in tg])
-                u.W_targ[y], u.b_targ[y] = W, b
-                arrays += [W, b]
-            u.scale = self._scale_p
-            u.log_alpha, u.alpha = self._la, ctypes.pointer(self._alpha_struct)
-            u.critic_loss, u.actor_loss, u.logp_mean = self._closs, self._aloss, self._lpm
-            u.workspace, u.workspace_bytes = self._ws, self._ws_bytes
+                arrays += _update_critic(u, y, self._critic_structs[y], self._critics[y], net, tg)
+            u.log_alpha, u.alpha, u.logp_mean = self._la, ctypes.pointer(self._alpha_struct), self._lpm
             # (the entry keeps alive what the struct points into, and the objects whose ids are the key)
             entry = cache[key] = (u, out, hb, arrays, her, pi, done)
         u, out = entry[0], entry[1]
@@ -829,19 +750,13 @@ class SacLearner(object):
         u.seed, u.target_entropy = self.seed, self.target_entropy        # read on every call, as actor_step reads them
         u.draw_counter = her._counter & 0xFFFFFFFFFFFFFFFF
         u.step_counter = self.counter & 0xFFFFFFFFFFFFFFFF
-        u.history = None if history is None else history.data_ptr()
-        s = stream.cuda_stream if stream is not None else self._raw_stream(self._index)
-        rc = self._lib.ctr_sac_update(u, updates, s)
-        if rc:
-            _abi.check(rc, "ctr_sac_update")
+        _update_call(self, self._lib.ctr_sac_update, "ctr_sac_update", u, updates, history, stream)
         her._log_alpha = self.log_alpha    # stays referenced until the next draw: the launches read it
         her._counter += updates
         self.counter += updates
-        pi._sources = list(self._actor.params)
-        pi.weights = pi.biases = pi.packed = None
+        _refreshed(pi, list(self._actor.params))
         for net, tg in done:
-            net._sources = tg
-            net.weights = net.biases = net.packed = None
+            _refreshed(net, tg)
         out = dict(out)
         if history is not None:
             out["history"] = history

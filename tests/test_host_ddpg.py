@@ -69,6 +69,14 @@ ROWS, ACTIONS, TARGET = 40 << 24, 41 << 24, 42 << 24
 NOARG = object()
 
 
+WRITES_IN_PLACE = " requires grad: the learner writes it in place, outside autograd"
+
+
+def exact(text):
+    """pytest.raises(match=...): the whole message and nothing else."""
+    return "^" + re.escape(text) + "$"
+
+
 def _critic_step(critic=NOARG, net=NOARG, adam=NOARG, rows=ROWS, actions=ACTIONS, scale=None, target=TARGET, B=64,
                  ws=WS, ws_bytes=WS_BYTES):
     _abi, lib = _lib()
@@ -96,7 +104,7 @@ def _both_refuse(word, **kw):
     """A refusal of an argument the two calls share."""
     for call, name in ((_critic_step, b"ctr_ddpg_critic_step"), (_actor_step, b"ctr_ddpg_actor_step")):
         rc, msg = call(**kw)
-        assert rc == -1 and name in msg and word in msg, (word, kw, rc, msg)
+        assert rc == -1 and msg == name + b": " + word, (word, kw, rc, msg)
 
 
 def test_declared_listed_and_exported():
@@ -152,10 +160,11 @@ def test_null_structs():
 
 
 def test_shapes():
-    _both_refuse(b"in_dim", critic=_critic(in_dim=24))
-    _both_refuse(b"n_hidden", critic=_critic(()))
-    _both_refuse(b"width", critic=_critic((64, 48)))
-    _both_refuse(b"CTR_ACTOR_MAX_BYTES", critic=_critic((256, 256)))
+    _both_refuse(b"critic: in_dim must be obs_dim + 12 = 25 or 26", critic=_critic(in_dim=24))
+    _both_refuse(b"critic: n_hidden must be in 1..CTR_ACTOR_MAX_HIDDEN (3)", critic=_critic(()))
+    _both_refuse(b"critic: every hidden width must be a multiple of 32 in 32..CTR_ACTOR_MAX_WIDTH (256)", critic=_critic((64, 48)))
+    _both_refuse(b"critic: the packed network (163840 B of weights + 2176 B of biases) exceeds CTR_ACTOR_MAX_BYTES = 98304 B of LDS",
+                 critic=_critic((256, 256)))
     for actor, word in ((_actor(in_dim=21), b"in_dim"), (_actor(()), b"n_hidden"), (_actor((64, 300)), b"width"),
                         (_actor(in_dim=20), b"actor->in_dim + 6")):
         rc, msg = _actor_step(actor=actor)
@@ -168,11 +177,12 @@ def test_shapes():
 
 def test_pointer_arrays_and_layers():
     for name in FIELDS:
-        _both_refuse(b"NULL pointer array", net=_net(**{name: None}))
-        _both_refuse(b"NULL layer", net=_net(**{name: _ptrs(50 << 24, holes=(2,))}))
+        _both_refuse(b"NULL pointer array or pow in net", net=_net(**{name: None}))
+        _both_refuse(b"NULL layer among W, b, gW, gb, mW, mb, vW, vb [0..n_hidden]",
+                     net=_net(**{name: _ptrs(50 << 24, holes=(2,))}))
         # two hidden layers: layer 3 is not read
         assert _critic_step(net=_net(**{name: _ptrs(50 << 24, holes=(3,))}), B=0)[0] == 0
-    _both_refuse(b"pow", net=_net(pow=None))
+    _both_refuse(b"NULL pointer array or pow in net", net=_net(pow=None))
     for kw in ({"cW": None}, {"cb": None}):
         rc, msg = _actor_step(**kw)
         assert rc == -1 and b"ctr_ddpg_actor_step" in msg and b"is NULL" in msg, msg
@@ -185,26 +195,26 @@ def test_aliases():
     for name in FIELDS[2:]:
         for param in ("W", "b"):
             same = _ptrs(60 << 24)
-            _both_refuse(b"is a parameter tensor", net=_net(**{name: same, param: same}))
+            _both_refuse(b"a gradient or state tensor is a parameter tensor", net=_net(**{name: same, param: same}))
     mixed = _ptrs(3 << 24)                                                 # gW's own pointers ...
     mixed[1] = (2 << 24) + 4096 * 2                                        # ... but layer 1's is b[2]
-    _both_refuse(b"is a parameter tensor", net=_net(gW=mixed))
-    _both_refuse(b"is a parameter tensor", net=_net(pow=(1 << 24) + 4096))  # pow is W[1]
+    _both_refuse(b"a gradient or state tensor is a parameter tensor", net=_net(gW=mixed))
+    _both_refuse(b"a gradient or state tensor is a parameter tensor", net=_net(pow=(1 << 24) + 4096))  # pow is W[1]
 
 
 def test_workspace():
     _both_refuse(b"workspace is NULL", ws=None)
-    _both_refuse(b"16-B aligned", ws=WS + 8)
+    _both_refuse(b"workspace must be 16-B aligned", ws=WS + 8)
     _abi, lib = _lib()
     a, c = _actor(), _critic()
     need = lib.ctr_ddpg_workspace_bytes(a, c, 64)
     assert need > 0
-    _both_refuse(b"workspace too small", ws_bytes=1024)
+    _both_refuse(b"workspace too small (ctr_ddpg_workspace_bytes)", ws_bytes=1024)
     rc, msg = _critic_step(ws_bytes=need - 1)                              # (the critic is the larger network here)
-    assert rc == -1 and b"workspace too small" in msg
+    assert rc == -1 and msg == b"ctr_ddpg_critic_step: workspace too small (ctr_ddpg_workspace_bytes)"
     assert _critic_step(ws_bytes=need, B=0)[0] == 0 and _actor_step(ws_bytes=need, B=0)[0] == 0
     rc, msg = _critic_step(ws_bytes=need, B=65)                            # one more tile than it was sized for
-    assert rc == -1 and b"workspace too small" in msg
+    assert rc == -1 and msg == b"ctr_ddpg_critic_step: workspace too small (ctr_ddpg_workspace_bytes)"
 
 
 def test_workspace_bytes():
@@ -227,17 +237,17 @@ def test_workspace_bytes():
 def test_adam_constants_and_b():
     nan, inf = float("nan"), float("inf")
     for kw in ({"lr": nan}, {"lr": inf}, {"beta1": nan}, {"beta2": -inf}, {"eps": inf}, {"eps": nan}):
-        _both_refuse(b"must be finite", adam=_adam(**kw))
+        _both_refuse(b"lr, beta1, beta2 and eps must be finite", adam=_adam(**kw))
     for kw in ({"beta1": -0.1}, {"beta1": 1.0}, {"beta2": 1.0}, {"beta2": 1.5}, {"beta2": -1e-3}):
-        _both_refuse(b"[0, 1)", adam=_adam(**kw))
+        _both_refuse(b"beta1 and beta2 must be in [0, 1)", adam=_adam(**kw))
     for eps in (0.0, -1e-8):
         _both_refuse(b"eps must be positive", adam=_adam(eps=eps))
     assert _critic_step(adam=_adam(beta1=0.0, beta2=0.0, lr=0.0), B=0)[0] == 0
     for B in (-1, 65537, 1 << 40):
-        _both_refuse(b"B must be", B=B)
+        _both_refuse(b"B must be in 0..65536", B=B)
     for kw in ({"rows": None}, {"actions": None}, {"target": None}):
         rc, msg = _critic_step(**kw)
-        assert rc == -1 and b"ctr_ddpg_critic_step" in msg and b"is NULL" in msg, msg
+        assert rc == -1 and msg == b"ctr_ddpg_critic_step: rows, actions or target is NULL", msg
     rc, msg = _actor_step(rows=None)
     assert rc == -1 and b"ctr_ddpg_actor_step" in msg and b"rows is NULL" in msg, msg
 
@@ -261,45 +271,47 @@ def test_learner_refuses_what_it_would_have_to_convert_or_could_not_write():
     import torch
     from ctr_reach_amd.learner import DdpgLearner
     policy, critic = _mlp(19, (64, 96), 6, True), _mlp(25, (32,), 1, False)
-    with pytest.raises(ValueError, match="policy layer 0: W requires grad"):
+    with pytest.raises(ValueError, match=exact("policy layer 0: W" + WRITES_IN_PLACE)):
         DdpgLearner(_mlp(19, (64,), 6, True, grad=True), critic)
-    with pytest.raises(ValueError, match="critic layer 0: W requires grad"):
+    with pytest.raises(ValueError, match=exact("critic layer 0: W" + WRITES_IN_PLACE)):
         DdpgLearner(policy, _mlp(25, (32,), 1, False, grad=True))
     half = _mlp(25, (32,), 1, False)
     half[2].bias.requires_grad_(True)
-    with pytest.raises(ValueError, match="critic layer 1: b requires grad"):
+    with pytest.raises(ValueError, match=exact("critic layer 1: b" + WRITES_IN_PLACE)):
         DdpgLearner(policy, half)
-    with pytest.raises(ValueError, match="nn.Tanh"):
+    with pytest.raises(ValueError, match=exact("the actor ends with nn.Tanh")):
         DdpgLearner(_mlp(19, (64,), 6, False), critic)
-    with pytest.raises(ValueError, match="output nn.Linear"):
+    with pytest.raises(ValueError, match=exact("the critic ends with its output nn.Linear (no activation after it)")):
         DdpgLearner(policy, _mlp(25, (32,), 1, True))
-    with pytest.raises(ValueError, match="19 or 20"):
+    with pytest.raises(ValueError, match=exact("the policy's rows are obs_dim + 6 = 19 or 20 floats")):
         DdpgLearner(_mlp(18, (64,), 6, True), critic)
-    with pytest.raises(ValueError, match="25 or 26"):
+    with pytest.raises(ValueError, match=exact("the critic's rows are obs_dim + 12 = 25 or 26 floats")):
         DdpgLearner(policy, _mlp(19, (64,), 1, False))
-    with pytest.raises(ValueError, match=r"19 \+ 6 inputs, not 26"):
+    with pytest.raises(ValueError, match=exact("the critic takes [row, action]: 19 + 6 inputs, not 26")):
         DdpgLearner(policy, _mlp(26, (32,), 1, False))
-    with pytest.raises(ValueError, match="multiples of 32"):
+    with pytest.raises(ValueError, match=exact("policy: hidden widths must be multiples of 32 in 32..256")):
         DdpgLearner(_mlp(19, (48,), 6, True), critic)
-    with pytest.raises(ValueError, match="hidden layers"):
+    with pytest.raises(ValueError, match=exact("the policy has 1..3 hidden layers and an output layer")):
         DdpgLearner(_mlp(19, (32, 32, 32, 32), 6, True), critic)
-    with pytest.raises(ValueError, match=r"policy layer 1: W must be \[6, 64\]"):
+    with pytest.raises(ValueError, match=exact("policy layer 1: W must be [6, 64], not [5, 64]")):
         DdpgLearner(_mlp(19, (64,), 5, True), critic)
-    with pytest.raises(ValueError, match="critic layer 1: b must be float32"):
+    with pytest.raises(ValueError, match=exact("critic layer 1: b must be float32, not torch.float64")):
         layers = [(m.weight, m.bias) for m in critic if hasattr(m, "weight")]
         DdpgLearner(policy, [layers[0], (layers[1][0], layers[1][1].double())])
-    with pytest.raises(ValueError, match="policy layer 0: W must be contiguous"):
+    with pytest.raises(ValueError, match=exact("policy layer 0: W must be contiguous")):
         DdpgLearner([(torch.zeros((19, 32)).t(), torch.zeros(32)), (torch.zeros((6, 32)), torch.zeros(6))], critic)
-    with pytest.raises(ValueError, match="must be a torch tensor"):
+    with pytest.raises(ValueError, match=exact("policy layer 0: W must be a torch tensor")):
         DdpgLearner([(np.zeros((32, 19), np.float32), torch.zeros(32)), (torch.zeros((6, 32)), torch.zeros(6))], critic)
-    for kw, word in (({"betas": (1.0, 0.999)}, "betas"), ({"betas": (0.9, -0.1)}, "betas"), ({"eps": 0.0}, "eps"),
-                     ({"eps": float("nan")}, "eps"), ({"actor_lr": float("inf")}, "actor_lr"),
-                     ({"critic_lr": float("nan")}, "critic_lr"), ({"max_batch": 0}, "max_batch"),
-                     ({"max_batch": 65537}, "max_batch"), ({"scale": [1.0] * 5}, "scale"),
-                     ({"scale": [1.0, 1.0, 0.0, 1.0, 1.0, 1.0]}, "scale")):
-        with pytest.raises(ValueError, match=word):
+    for kw, word in (({"betas": (1.0, 0.999)}, "betas must be in [0, 1)"), ({"betas": (0.9, -0.1)}, "betas must be in [0, 1)"),
+                     ({"eps": 0.0}, "eps must be positive"), ({"eps": float("nan")}, "eps must be finite"),
+                     ({"actor_lr": float("inf")}, "actor_lr must be finite"),
+                     ({"critic_lr": float("nan")}, "critic_lr must be finite"),
+                     ({"max_batch": 0}, "max_batch must be in 1..65536"), ({"max_batch": 65537}, "max_batch must be in 1..65536"),
+                     ({"scale": [1.0] * 5}, "scale is six finite, non-zero floats"),
+                     ({"scale": [1.0, 1.0, 0.0, 1.0, 1.0, 1.0]}, "scale is six finite, non-zero floats")):
+        with pytest.raises(ValueError, match=exact(word)):
             DdpgLearner(policy, critic, **kw)
-    with pytest.raises(ValueError, match="on a GPU"):                      # (everything else was in order)
+    with pytest.raises(ValueError, match=exact("the networks are on cpu: the learner's networks are on a GPU")):   # (all else in order)
         DdpgLearner(policy, critic, scale=[0.001] * 3 + [0.087] * 3)
 
 

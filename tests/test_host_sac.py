@@ -15,6 +15,7 @@ import pytest
 import ddpg_ref as R
 import sac_ref as S
 import test_host_td3 as H
+from test_host_ddpg import WRITES_IN_PLACE, exact
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FNS = ("ctr_gauss_blob_bytes", "ctr_gauss_pack", "ctr_gauss_load", "ctr_gauss_act", "ctr_sac_workspace_bytes",
@@ -489,23 +490,27 @@ def test_sac_learner_constructor_errors():
     from ctr_reach_amd.learner import SacLearner
     policy, c1, c2, _ = S.make(0, (32,), (32,), (64,), 19, 4)
     six = R.mlp(19, (32,), 6, True).requires_grad_(False)
-    with pytest.raises(ValueError, match=r"\[12, 32\]"):
+    with pytest.raises(ValueError, match=exact("policy layer 1: W must be [12, 32], not [6, 32]")):
         SacLearner(six[:-1], c1, c2)
-    with pytest.raises(ValueError, match="ends with its output"):
+    with pytest.raises(ValueError, match=exact("the policy ends with its output nn.Linear (no activation after it)")):
         SacLearner(six, c1, c2)
-    with pytest.raises(ValueError, match="19 \\+ 6 inputs"):
+    with pytest.raises(ValueError, match=exact("the critic2 takes [row, action]: 19 + 6 inputs, not 26")):
         SacLearner(policy, c1, R.mlp(26, (32,), 1, False).requires_grad_(False))
-    with pytest.raises(ValueError, match="requires grad"):
+    with pytest.raises(ValueError, match=exact("policy layer 0: W" + WRITES_IN_PLACE)):
         SacLearner(copy_with_grad(policy), c1, c2)
-    with pytest.raises(ValueError, match="share a tensor"):
+    with pytest.raises(ValueError, match=exact("critic1 and critic2 share a tensor: the twin step updates them side by side")):
         SacLearner(policy, c1, c1)
-    for kw, word in (({"alpha_lr": float("nan")}, "alpha_lr"), ({"target_entropy": float("inf")}, "target_entropy"),
-                     ({"init_alpha": 0.0}, "init_alpha"), ({"init_alpha": float("inf")}, "init_alpha"),
-                     ({"betas": (0.9, 1.0)}, "betas"), ({"eps": 0.0}, "eps"), ({"max_batch": 0}, "max_batch"),
-                     ({"max_batch": 65537}, "max_batch"), ({"scale": [1, 2, 3]}, "scale"), ({"scale": [1, 2, 3, 0, 1, 1]}, "scale")):
-        with pytest.raises(ValueError, match=word):
+    for kw, word in (({"alpha_lr": float("nan")}, "alpha_lr must be finite"),
+                     ({"target_entropy": float("inf")}, "target_entropy must be finite"),
+                     ({"init_alpha": 0.0}, "init_alpha must be positive and finite"),
+                     ({"init_alpha": float("inf")}, "init_alpha must be positive and finite"),
+                     ({"betas": (0.9, 1.0)}, "betas must be in [0, 1)"), ({"eps": 0.0}, "eps must be positive"),
+                     ({"max_batch": 0}, "max_batch must be in 1..65536"), ({"max_batch": 65537}, "max_batch must be in 1..65536"),
+                     ({"scale": [1, 2, 3]}, "scale is six finite, non-zero floats"),
+                     ({"scale": [1, 2, 3, 0, 1, 1]}, "scale is six finite, non-zero floats")):
+        with pytest.raises(ValueError, match=exact(word)):
             SacLearner(policy, c1, c2, **kw)
-    with pytest.raises(ValueError, match="on a GPU"):
+    with pytest.raises(ValueError, match=exact("the networks are on cpu: the learner's networks are on a GPU")):
         SacLearner(policy, c1, c2)
     assert all(not p.requires_grad for p in policy.parameters()) and isinstance(policy[0].weight, torch.Tensor)
 

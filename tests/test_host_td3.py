@@ -13,6 +13,8 @@ import types
 import numpy as np
 import pytest
 
+from test_host_ddpg import WRITES_IN_PLACE, exact
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FNS = ("ctr_her_sample_td3", "ctr_td3_workspace_bytes", "ctr_td3_critic_step")
 
@@ -246,7 +248,7 @@ def _step(critics=NOARG, nets=NOARG, adam=NOARG, rows=ROWS, actions=ACTIONS, sca
 
 def _step_refused(word, **kw):
     rc, msg = _step(**kw)
-    assert rc == -1 and b"ctr_td3_critic_step" in msg and word in msg, (word, kw, rc, msg)
+    assert rc == -1 and msg == word, (word, kw, rc, msg)
 
 
 def test_a_good_twin_step_gets_to_b_zero():
@@ -257,45 +259,51 @@ def test_a_good_twin_step_gets_to_b_zero():
 
 
 def test_twin_step_refuses_null_arrays_and_entries():
-    _step_refused(b"is NULL", critics=None)
-    _step_refused(b"is NULL", nets=None)
-    _step_refused(b"NULL entry", critics=(_critic(), None))
-    _step_refused(b"NULL entry", critics=(None, _critic()))
-    _step_refused(b"NULL entry", nets=(_net(0), None))
-    _step_refused(b"NULL entry", nets=(None, _net(1)))
-    _step_refused(b"adam is NULL", adam=None)
+    _step_refused(b"ctr_td3_critic_step: critic or net is NULL", critics=None)
+    _step_refused(b"ctr_td3_critic_step: critic or net is NULL", nets=None)
+    _step_refused(b"ctr_td3_critic_step: NULL entry in critic[2] or net[2]", critics=(_critic(), None))
+    _step_refused(b"ctr_td3_critic_step: NULL entry in critic[2] or net[2]", critics=(None, _critic()))
+    _step_refused(b"ctr_td3_critic_step: NULL entry in critic[2] or net[2]", nets=(_net(0), None))
+    _step_refused(b"ctr_td3_critic_step: NULL entry in critic[2] or net[2]", nets=(None, _net(1)))
+    _step_refused(b"ctr_td3_critic_step: adam is NULL", adam=None)
 
 
 def test_twin_step_refuses_for_either_net_what_the_single_step_refuses():
     good = _critic()
-    for bad, word in ((_critic(in_dim=24), b"in_dim"), (_critic(()), b"n_hidden"), (_critic((64, 48)), b"width"),
-                      (_critic((256, 256)), b"CTR_ACTOR_MAX_BYTES")):
+    fn = b"ctr_td3_critic_step: critic: "
+    for bad, word in ((_critic(in_dim=24), fn + b"in_dim must be obs_dim + 12 = 25 or 26"),
+                      (_critic(()), fn + b"n_hidden must be in 1..CTR_ACTOR_MAX_HIDDEN (3)"),
+                      (_critic((64, 48)), fn + b"every hidden width must be a multiple of 32 in 32..CTR_ACTOR_MAX_WIDTH (256)"),
+                      (_critic((256, 256)), fn + b"the packed network (163840 B of weights + 2176 B of biases) exceeds "
+                                                 b"CTR_ACTOR_MAX_BYTES = 98304 B of LDS")):
         _step_refused(word, critics=(bad, good))
         _step_refused(word, critics=(good, bad))
-    _step_refused(b"same in_dim", critics=(_critic(), _critic(in_dim=26)))
+    _step_refused(b"ctr_td3_critic_step: the two critics must have the same in_dim", critics=(_critic(), _critic(in_dim=26)))
     for which in (0, 1):
         def nets(**over):
             pair = [_net(0), _net(1)]
             pair[which] = _net(which, **over)
             return tuple(pair)
         for name in FIELDS:
-            _step_refused(b"NULL pointer array", nets=nets(**{name: None}))
+            _step_refused(b"ctr_td3_critic_step: NULL pointer array or pow in net", nets=nets(**{name: None}))
             # critic 0 has two hidden layers (layers 0..2 are read), critic 1 one (layers 0..1)
-            _step_refused(b"NULL layer", nets=nets(**{name: _ptrs(50 << 24, holes=(1,))}))
-        _step_refused(b"pow", nets=nets(pow=None))
+            _step_refused(b"ctr_td3_critic_step: NULL layer among W, b, gW, gb, mW, mb, vW, vb [0..n_hidden]",
+                          nets=nets(**{name: _ptrs(50 << 24, holes=(1,))}))
+        _step_refused(b"ctr_td3_critic_step: NULL pointer array or pow in net", nets=nets(pow=None))
         same = _ptrs(60 << 24)
-        _step_refused(b"is a parameter tensor", nets=nets(gW=same, W=same))
-        _step_refused(b"is a parameter tensor", nets=nets(pow=((16 * which + 1) << 24) + 4096))   # pow is W[1]
+        _step_refused(b"ctr_td3_critic_step: a gradient or state tensor is a parameter tensor", nets=nets(gW=same, W=same))
+        _step_refused(b"ctr_td3_critic_step: a gradient or state tensor is a parameter tensor",
+                      nets=nets(pow=((16 * which + 1) << 24) + 4096))  # pow is W[1]
     assert _step(B=0, nets=(_net(0), _net(1, W=_ptrs(50 << 24, holes=(2,)))))[0] == 0        # layer 2 of critic 1 is not read
     nan, inf = float("nan"), float("inf")
     for kw in ({"lr": nan}, {"beta1": inf}, {"eps": nan}):
-        _step_refused(b"must be finite", adam=_adam(**kw))
-    _step_refused(b"[0, 1)", adam=_adam(beta1=1.0))
-    _step_refused(b"eps must be positive", adam=_adam(eps=0.0))
+        _step_refused(b"ctr_td3_critic_step: lr, beta1, beta2 and eps must be finite", adam=_adam(**kw))
+    _step_refused(b"ctr_td3_critic_step: beta1 and beta2 must be in [0, 1)", adam=_adam(beta1=1.0))
+    _step_refused(b"ctr_td3_critic_step: eps must be positive", adam=_adam(eps=0.0))
     for B in (-1, 65537, 1 << 40):
-        _step_refused(b"B must be", B=B)
+        _step_refused(b"ctr_td3_critic_step: B must be in 0..65536", B=B)
     for kw in ({"rows": None}, {"actions": None}, {"target": None}):
-        _step_refused(b"is NULL", **kw)
+        _step_refused(b"ctr_td3_critic_step: rows, actions or target is NULL", **kw)
 
 
 def test_twin_step_refuses_nets_that_share_a_tensor():
@@ -304,28 +312,31 @@ def test_twin_step_refuses_nets_that_share_a_tensor():
         for other in FIELDS:
             arr = _ptrs((16 + FIELDS.index(other) + 1) << 24)              # net 1's own array of `other` ...
             arr[1] = ctypes.cast(getattr(first, name), ctypes.POINTER(ctypes.c_void_p))[0]   # ... layer 1: net 0's `name`[0]
-            _step_refused(b"share", nets=(first, _net(1, **{other: arr})))
-    _step_refused(b"share", nets=(first, _net(1, pow=first.pow)))
-    _step_refused(b"share", nets=(first, _net(1, pow=(3 << 24) + 4096)))       # net 1's pow is net 0's gW[1]
+            _step_refused(b"ctr_td3_critic_step: the two nets share a parameter, gradient or state tensor",
+                          nets=(first, _net(1, **{other: arr})))
+    _step_refused(b"ctr_td3_critic_step: the two nets share a tensor (pow)", nets=(first, _net(1, pow=first.pow)))
+    _step_refused(b"ctr_td3_critic_step: the two nets share a parameter, gradient or state tensor",
+                  nets=(first, _net(1, pow=(3 << 24) + 4096)))  # net 1's pow is net 0's gW[1]
     arr = _ptrs((16 + 5) << 24)
     arr[0] = first.pow                                                     # net 1's mW[0] is net 0's pow
-    _step_refused(b"share", nets=(first, _net(1, mW=arr)))
-    _step_refused(b"share", nets=(first, first))
+    _step_refused(b"ctr_td3_critic_step: the two nets share a parameter, gradient or state tensor", nets=(first, _net(1, mW=arr)))
+    _step_refused(b"ctr_td3_critic_step: the two nets share a tensor (pow)", nets=(first, first))
 
 
 def test_twin_step_workspace():
     _abi, lib = _lib()
-    _step_refused(b"workspace is NULL", ws=None)
-    _step_refused(b"16-B aligned", ws=WS + 8)
+    _step_refused(b"ctr_td3_critic_step: workspace is NULL", ws=None)
+    _step_refused(b"ctr_td3_critic_step: workspace must be 16-B aligned", ws=WS + 8)
     a, c1, c2 = _actor((32,)), _critic(), _critic((32,))
     need = lib.ctr_td3_workspace_bytes(a, c1, c2, 64)
     one = lib.ctr_ddpg_workspace_bytes(a, c1, 64)
     assert need > one > 0
-    _step_refused(b"workspace too small", ws_bytes=1024)
-    _step_refused(b"workspace too small", ws_bytes=one)                    # room for critic 1 alone
-    _step_refused(b"workspace too small", ws_bytes=need - 1)
+    _step_refused(b"ctr_td3_critic_step: workspace too small (ctr_ddpg_workspace_bytes)", ws_bytes=1024)
+    _step_refused(b"ctr_td3_critic_step: workspace too small (ctr_td3_workspace_bytes)", ws_bytes=one)  # room for critic 1 alone
+    _step_refused(b"ctr_td3_critic_step: workspace too small (ctr_td3_workspace_bytes)", ws_bytes=need - 1)
     assert _step(ws_bytes=need, B=0)[0] == 0
-    _step_refused(b"workspace too small", ws_bytes=need, B=65)             # one more tile than it was sized for
+    _step_refused(b"ctr_td3_critic_step: workspace too small (ctr_ddpg_workspace_bytes)",
+                  ws_bytes=need, B=65)  # one more tile than it was sized for
 
 
 SHAPE_PAIRS = [((64, 64), (32,)), ((32,), (32,)), ((64, 96), (32,)), ((128, 128, 128), (256, 128))]
@@ -430,49 +441,51 @@ def test_learner_refuses_what_it_would_have_to_convert_or_could_not_write():
     import torch
     from ctr_reach_amd.learner import Td3Learner
     policy, c1, c2 = _mlp(19, (64, 96), 6, True), _mlp(25, (32,), 1, False), _mlp(25, (64, 32), 1, False)
-    with pytest.raises(ValueError, match="policy layer 0: W requires grad"):
+    with pytest.raises(ValueError, match=exact("policy layer 0: W" + WRITES_IN_PLACE)):
         Td3Learner(_mlp(19, (64,), 6, True, grad=True), c1, c2)
-    with pytest.raises(ValueError, match="critic1 layer 0: W requires grad"):
+    with pytest.raises(ValueError, match=exact("critic1 layer 0: W" + WRITES_IN_PLACE)):
         Td3Learner(policy, _mlp(25, (32,), 1, False, grad=True), c2)
     half = _mlp(25, (32,), 1, False)
     half[2].bias.requires_grad_(True)
-    with pytest.raises(ValueError, match="critic2 layer 1: b requires grad"):
+    with pytest.raises(ValueError, match=exact("critic2 layer 1: b" + WRITES_IN_PLACE)):
         Td3Learner(policy, c1, half)
-    with pytest.raises(ValueError, match="nn.Tanh"):
+    with pytest.raises(ValueError, match=exact("the actor ends with nn.Tanh")):
         Td3Learner(_mlp(19, (64,), 6, False), c1, c2)
-    with pytest.raises(ValueError, match="output nn.Linear"):
+    with pytest.raises(ValueError, match=exact("the critic2 ends with its output nn.Linear (no activation after it)")):
         Td3Learner(policy, c1, _mlp(25, (32,), 1, True))
-    with pytest.raises(ValueError, match="19 or 20"):
+    with pytest.raises(ValueError, match=exact("the policy's rows are obs_dim + 6 = 19 or 20 floats")):
         Td3Learner(_mlp(18, (64,), 6, True), c1, c2)
-    with pytest.raises(ValueError, match="25 or 26"):
+    with pytest.raises(ValueError, match=exact("the critic1's rows are obs_dim + 12 = 25 or 26 floats")):
         Td3Learner(policy, _mlp(19, (64,), 1, False), c2)
-    with pytest.raises(ValueError, match=r"critic2 takes \[row, action\]: 19 \+ 6 inputs, not 26"):
+    with pytest.raises(ValueError, match=exact("the critic2 takes [row, action]: 19 + 6 inputs, not 26")):
         Td3Learner(policy, c1, _mlp(26, (32,), 1, False))
-    with pytest.raises(ValueError, match="multiples of 32"):
+    with pytest.raises(ValueError, match=exact("critic1: hidden widths must be multiples of 32 in 32..256")):
         Td3Learner(policy, _mlp(25, (48,), 1, False), c2)
-    with pytest.raises(ValueError, match="hidden layers"):
+    with pytest.raises(ValueError, match=exact("the critic2 has 1..3 hidden layers and an output layer")):
         Td3Learner(policy, c1, _mlp(25, (32, 32, 32, 32), 1, False))
-    with pytest.raises(ValueError, match="critic2 layer 1: b must be float32"):
+    with pytest.raises(ValueError, match=exact("critic2 layer 1: b must be float32, not torch.float64")):
         layers = [(m.weight, m.bias) for m in c1 if hasattr(m, "weight")]
         Td3Learner(policy, c1, [layers[0], (layers[1][0], layers[1][1].double())])
-    with pytest.raises(ValueError, match="critic1 layer 0: W must be contiguous"):
+    with pytest.raises(ValueError, match=exact("critic1 layer 0: W must be contiguous")):
         Td3Learner(policy, [(torch.zeros((25, 32)).t(), torch.zeros(32)), (torch.zeros((1, 32)), torch.zeros(1))], c2)
-    with pytest.raises(ValueError, match="must be a torch tensor"):
+    with pytest.raises(ValueError, match=exact("critic2 layer 0: W must be a torch tensor")):
         Td3Learner(policy, c1, [(np.zeros((32, 25), np.float32), torch.zeros(32)), (torch.zeros((1, 32)), torch.zeros(1))])
-    with pytest.raises(ValueError, match="share a tensor"):
+    with pytest.raises(ValueError, match=exact("critic1 and critic2 share a tensor: the twin step updates them side by side")):
         Td3Learner(policy, c1, c1)
     layers = [(m.weight, m.bias) for m in c1 if hasattr(m, "weight")]
     other = [(m.weight, m.bias) for m in _mlp(25, (32,), 1, False) if hasattr(m, "weight")]
-    with pytest.raises(ValueError, match="share a tensor"):
+    with pytest.raises(ValueError, match=exact("critic1 and critic2 share a tensor: the twin step updates them side by side")):
         Td3Learner(policy, layers, [other[0], (other[1][0], layers[1][1])])
-    for kw, word in (({"betas": (1.0, 0.999)}, "betas"), ({"betas": (0.9, -0.1)}, "betas"), ({"eps": 0.0}, "eps"),
-                     ({"eps": float("nan")}, "eps"), ({"actor_lr": float("inf")}, "actor_lr"),
-                     ({"critic_lr": float("nan")}, "critic_lr"), ({"max_batch": 0}, "max_batch"),
-                     ({"max_batch": 65537}, "max_batch"), ({"scale": [1.0] * 5}, "scale"),
-                     ({"scale": [1.0, 1.0, 0.0, 1.0, 1.0, 1.0]}, "scale")):
-        with pytest.raises(ValueError, match=word):
+    for kw, word in (({"betas": (1.0, 0.999)}, "betas must be in [0, 1)"), ({"betas": (0.9, -0.1)}, "betas must be in [0, 1)"),
+                     ({"eps": 0.0}, "eps must be positive"), ({"eps": float("nan")}, "eps must be finite"),
+                     ({"actor_lr": float("inf")}, "actor_lr must be finite"),
+                     ({"critic_lr": float("nan")}, "critic_lr must be finite"),
+                     ({"max_batch": 0}, "max_batch must be in 1..65536"), ({"max_batch": 65537}, "max_batch must be in 1..65536"),
+                     ({"scale": [1.0] * 5}, "scale is six finite, non-zero floats"),
+                     ({"scale": [1.0, 1.0, 0.0, 1.0, 1.0, 1.0]}, "scale is six finite, non-zero floats")):
+        with pytest.raises(ValueError, match=exact(word)):
             Td3Learner(policy, c1, c2, **kw)
-    with pytest.raises(ValueError, match="on a GPU"):                      # (everything else was in order)
+    with pytest.raises(ValueError, match=exact("the networks are on cpu: the learner's networks are on a GPU")):   # (all else in order)
         Td3Learner(policy, c1, c2, scale=[0.001] * 3 + [0.087] * 3)
 
 
